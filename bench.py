@@ -16,6 +16,11 @@ Topology (weak scaling):
 One "step" = one microbatch (batch 32) through forward+backward+optimizer on
 BOTH stages of every pipeline.  Timed region: barrier+sync, run K steps to
 full pipeline drain, barrier+sync; value = K * 32 * n_pipelines / elapsed_max.
+
+A plain run does only that: set-up, warmup, the K timed steps, one JSON result
+line.  --dump-outputs DIR also writes what the last timed step computed as
+.npy files (inputs are seeded, so two builds can be compared output for
+output); --full is where any measurement beyond the headline figure belongs.
 """
 
 from __future__ import annotations
@@ -66,8 +71,43 @@ def make_batches(device, n, seed=0):
         gp = torch.Generator(device="cpu").manual_seed(777)
         _LABEL_PROJ = torch.randn(3 * 32 * 32, 10, generator=gp).to(device)
     with torch.no_grad():
-        y = (x.reshape(n * BATCH, -1) @ _LABEL_PROJ).argmax(-1).reshape(n, BATCH)
+        y = (x.reshape(n * BATCH, 3 * 32 * 32) @ _LABEL_PROJ).argmax(-1).reshape(n, BATCH)
     return x, y
+
+
+DUMP_SAMPLE_ELEMS = 1 << 20   # per-array cap: larger arrays are sampled
+DUMP_SAMPLE_SEED = 20240607
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _stage_state(prefix, model):
+    """Parameters and buffers (BN running stats) a caller holds after a step."""
+    return {f"{prefix}.{k}": v for k, v in model.state_dict().items()}
+
+
+def dump_outputs(out_dir, tensors):
+    """Write each tensor as <out_dir>/<name>.npy (float32, or float64 for
+    integer/double data).  Arrays above DUMP_SAMPLE_ELEMS are reduced to a
+    fixed seeded sample of their flattened elements (same indices every run,
+    keyed by position in the name-sorted list) so the whole dump stays under
+    DUMP_MAX_BYTES and two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for idx, name in enumerate(sorted(tensors)):
+        t = tensors[name].detach().to("cpu")
+        t = t.to(torch.float32 if t.dtype in (torch.float32, torch.float16,
+                                              torch.bfloat16) else torch.float64)
+        a = t.contiguous().numpy()
+        if a.size > DUMP_SAMPLE_ELEMS:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED + idx)
+            pick = np.sort(rng.choice(a.size, DUMP_SAMPLE_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs would exceed {DUMP_MAX_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] wrote {len(tensors)} arrays ({total / 2**20:.1f} MiB) to {out_dir}")
 
 
 class ColocatedPipeline:
@@ -90,6 +130,17 @@ class ColocatedPipeline:
         self.use_graphs = use_graphs and device.type == "cuda"
         self.graph = None
         self.batch_seed = 0
+        self.last_logits = None
+        self.last_loss = None
+
+    def outputs(self):
+        """What the last step handed back: its logits and loss, and both
+        stages' updated parameters/buffers.  Under graph replay the logits and
+        loss are the captured step's static tensors, rewritten every replay."""
+        out = {"logits": self.last_logits, "loss": self.last_loss}
+        out.update(_stage_state("stage1", self.s1_model))
+        out.update(_stage_state("stage2", self.s2_model))
+        return out
 
     def _ce(self, logits, labels):
         if logits.is_cuda:
@@ -112,6 +163,7 @@ class ColocatedPipeline:
             act_in = act0.detach().requires_grad_(True)
         logits = self.s2_model(act_in)
         loss = self._ce(logits, self.y_buf)
+        self.last_logits, self.last_loss = logits, loss
         self.nan_flag |= torch.isnan(loss)
         loss.backward()
         self.s2_opt.step()
@@ -155,6 +207,14 @@ class ColocatedPipeline:
         self.batch_seed += 1
         xs, ys = make_batches(self.device, steps, seed=self.batch_seed)
         if self.use_graphs and self.graph is None:
+            # Stage a real batch before the capture warm steps train on the
+            # buffers.  Left at zero, every BN sees zero variance (invstd =
+            # 1/sqrt(eps)), the only signal is the split-K atomics' rounding
+            # noise amplified ~300x per layer, and those three updates — and
+            # everything computed after them — differ from run to run.
+            x0, y0 = (xs, ys) if steps > 0 else make_batches(self.device, 1, seed=0)
+            self.x_buf.copy_(x0[0])
+            self.y_buf.copy_(y0[0])
             try:
                 self._capture()
                 log("[bench] hipGraph capture of the full step: ok")
@@ -192,6 +252,10 @@ class OverlapPipeline:
         self.sB = torch.cuda.Stream()
         self.nan_flag = torch.zeros((), dtype=torch.bool, device=device)
         self.batch_seed = 0
+        self.last_logits = None
+        self.last_loss = None
+
+    outputs = ColocatedPipeline.outputs
 
     def _drain_one(self, pending):
         out1, act, ev_b = pending.popleft()
@@ -220,6 +284,7 @@ class OverlapPipeline:
                 act = out1.detach().requires_grad_(True)
                 logits = self.s2_model(act)
                 loss = self._ce(logits, ys[i])
+                self.last_logits, self.last_loss = logits, loss
                 self.nan_flag |= torch.isnan(loss)
                 loss.backward()
                 self.s2_opt.step()
@@ -270,6 +335,18 @@ class DistPipeline:
                                  group_fwd=gf, group_bwd=gb,
                                  depth=CONTROL_COUNT + 1)
         self.next_id = 1
+        self.last_logits = None
+        self.last_loss = None
+
+    def outputs(self):
+        """This rank's share: its stage's updated parameters/buffers, plus the
+        last step's logits and loss on stage-2 ranks."""
+        stage = "stage1" if self.is_first else "stage2"
+        out = _stage_state(f"rank{self.rank}.{stage}", self.model)
+        if not self.is_first:
+            out[f"rank{self.rank}.logits"] = self.last_logits
+            out[f"rank{self.rank}.loss"] = self.last_loss
+        return out
 
     # a wedged peer (bad comm init, lost message) surfaces as a named
     # TimeoutError with the rank/peer in it instead of hanging the driver run
@@ -324,6 +401,7 @@ class DistPipeline:
                 logits = self.model(act)
                 loss = hf.cross_entropy(logits, m.labels) if logits.is_cuda else \
                     torch.nn.functional.cross_entropy(logits, m.labels)
+                self.last_logits, self.last_loss = logits, loss
                 nan_flag |= torch.isnan(loss)
                 loss.backward()
                 self.opt.step()
@@ -365,7 +443,19 @@ def main():
                          "recomputing (one fewer stage-1 forward per step — "
                          "NOT the production pipeline's per-microbatch work; "
                          "labeled mode=serial-stash in the JSON)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed (logits, loss, both stages' updated "
+                         "parameters and buffers) as DIR/<name>.npy; arrays "
+                         "over 2^20 elements are a fixed seeded sample; "
+                         "with N>=2 only the first pipeline's two ranks dump")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond the "
+                         "headline figure (nothing at present: a plain run is "
+                         "already set-up, warmup, timed steps, result line)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -437,6 +527,11 @@ def main():
 
     if bool(nan_flag.item()):
         log("WARNING: NaN loss during timed region")
+
+    # under torchrun only pipeline 0 (ranks 0 and world/2) dumps, so the
+    # whole dump stays one model's worth whatever the GPU count
+    if args.dump_outputs and (not dist_mode or rank in (0, world // 2)):
+        dump_outputs(args.dump_outputs, pipeline.outputs())
 
     if rank == 0:
         print(json.dumps({

@@ -432,11 +432,14 @@ static void slab_reduce(const at::Tensor& slab, int splits, at::Tensor& out,
 
 // slab mode threshold: slab stores beat atomics once MANY splits pile on
 // one output; at mild splits (<8) the reduce pass's launch+ramp overhead
-// loses to cheap atomics (bench sweep, profiles/SUMMARY.md round 2)
+// loses slightly to cheap atomics (bench sweep, profiles/SUMMARY.md round 2).
+// The default is still 3: atomic accumulation of three or more partial sums
+// depends on arrival order, so results changed from run to run (two splits
+// commute), and training amplifies that noise; slabs reduce in fixed order.
 static inline int slab_min_splits() {
   static int v = [] {
     const char* e = std::getenv("SLK_SLAB_MIN");
-    return e ? atoi(e) : 8;
+    return e ? atoi(e) : 3;
   }();
   return v < 2 ? 2 : v;
 }

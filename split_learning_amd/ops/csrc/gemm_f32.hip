@@ -57,9 +57,10 @@ struct StridedStore {
   long sCb;
   int N;
   const float* bias;  // per-column bias (nullable)
-  bool accumulate;    // atomic accumulate (split-K or beta=1)
+  bool accumulate;    // atomic accumulate into C (beta=1; one add per element)
+  long slab_stride;   // > 0: split ks stores into its own slab (no atomics)
   __device__ void store(int b, int m, int n, float v, int ks) const {
-    float* p = C + (long)b * sCb + (long)m * N + n;
+    float* p = C + (long)ks * slab_stride + (long)b * sCb + (long)m * N + n;
     if (bias != nullptr && ks == 0) v += bias[n];
     if (accumulate) {
       atomicAdd(p, v);
@@ -69,6 +70,21 @@ struct StridedStore {
   }
 };
 
+// out[i] = sum_s slab[s*numel + i] in fixed order: split-K partial sums are
+// added the same way every run (atomic accumulation is order-dependent for
+// three or more splits, and training amplifies that rounding noise)
+__global__ void gemm_slab_reduce_kernel(const float* __restrict__ slab, int splits,
+                                        float* __restrict__ out, long numel) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < numel;
+       i += stride) {
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += slab[(long)k * numel + i];
+    out[i] = s;
+  }
+}
+
+// split_k > 1: every split writes its own slab, reduced into c afterwards
 static void launch_strided(const at::Tensor& a2, const at::Tensor& b2, at::Tensor& c,
                            bool ta, bool tb, const c10::optional<at::Tensor>& bias,
                            bool accumulate, int split_k) {
@@ -88,15 +104,28 @@ static void launch_strided(const at::Tensor& a2, const at::Tensor& b2, at::Tenso
   g.sBk = tb ? b2.stride(-1) : b2.stride(-2);
   g.sBn = tb ? b2.stride(-2) : b2.stride(-1);
 
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  // the launcher BK-aligns the split: size the slab by the effective count
+  split_k = slk_effective_split(K, split_k);
+  TORCH_CHECK(!(accumulate && split_k > 1), "split-K cannot accumulate into C");
+  const long numel = (long)nb * M * N;
+  at::Tensor slab;
+  if (split_k > 1) slab = at::empty({(long)split_k * numel}, c.options());
+
   StridedStore st;
-  st.C = c.data_ptr<float>();
+  st.C = split_k > 1 ? slab.data_ptr<float>() : c.data_ptr<float>();
   st.sCb = batched ? (long)M * N : 0;
   st.N = N;
   st.bias = bias.has_value() ? bias->data_ptr<float>() : nullptr;
-  st.accumulate = accumulate || split_k > 1;
+  st.accumulate = accumulate;
+  st.slab_stride = split_k > 1 ? numel : 0;
 
-  auto stream = c10::hip::getCurrentHIPStream().stream();
   slk_launch_gemm(g, st, M, N, K, nb, split_k, stream, slk_use_big(M, N));
+  if (split_k > 1) {
+    const int grid = (int)std::min<long>((numel + 255) / 256, 4096);
+    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3(grid), dim3(256), 0, stream,
+                       slab.data_ptr<float>(), split_k, c.data_ptr<float>(), numel);
+  }
 }
 
 at::Tensor matmul_f32(const at::Tensor& a, const at::Tensor& b, bool ta, bool tb,
@@ -127,10 +156,6 @@ at::Tensor matmul_f32(const at::Tensor& a, const at::Tensor& b, bool ta, bool tb
     const int bm = slk_use_big(M, N) ? SLK_BM2 : SLK_BM;
     const int bn = slk_use_big(M, N) ? SLK_BN2 : SLK_BN;
     split_k = slk_pick_split_k(M, N, Ka, a.dim() == 3 ? a.size(0) : 1, bm, bn);
-    if (split_k > 1) {
-      slk_zero_async(c.data_ptr<float>(), c.numel(),
-                     c10::hip::getCurrentHIPStream().stream());
-    }
   }
   launch_strided(a, b, c, ta, tb, c10::nullopt, accumulate, split_k);
   return c;
@@ -150,8 +175,7 @@ at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w,
   const bool big = slk_use_big(M, N);
   int split_k = slk_pick_split_k(M, N, K, 1, big ? SLK_BM2 : SLK_BM,
                                  big ? SLK_BN2 : SLK_BN);
-  auto y = split_k > 1 ? zeroed({M, N}, x.options())
-                       : at::empty({M, N}, x.options());
+  auto y = at::empty({M, N}, x.options());
   launch_strided(x, w, y, /*ta=*/false, /*tb=*/true, bias, /*acc=*/false, split_k);
   return y;
 }

@@ -78,7 +78,10 @@ at::Tensor softmax_bwd(const at::Tensor& gy, const at::Tensor& y) {
 }
 
 // fused CE forward: probs[b] = softmax(logits[b]); loss = mean(-log p[label]).
-// One wave per row; loss accumulated via atomicAdd into a zeroed scalar.
+// One wave per row, each wave summing its rows in order.  A single-block
+// launch (small B) adds the waves' sums in fixed order and stores the loss,
+// so it is the same every run; multi-block launches atomicAdd into a zeroed
+// scalar.
 __global__ void ce_fwd_kernel(const float* __restrict__ logits,
                               const int64_t* __restrict__ labels,
                               float* __restrict__ probs, float* __restrict__ loss,
@@ -86,6 +89,8 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int waves = blockDim.x >> 6;
+  __shared__ float wave_sum[16];
+  float acc = 0.f;
   for (int row = blockIdx.x * waves + wid; row < B; row += gridDim.x * waves) {
     const float* xr = logits + (long)row * C;
     float* pr = probs + (long)row * C;
@@ -104,8 +109,19 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
     if (lane == 0) {
       const int64_t lbl = labels[row];
       const float lse = m + logf(s);
-      atomicAdd(loss, (lse - xr[lbl]) / (float)B);
+      acc += (lse - xr[lbl]) / (float)B;
     }
+  }
+  if (gridDim.x > 1) {
+    if (lane == 0 && acc != 0.f) atomicAdd(loss, acc);
+    return;
+  }
+  if (lane == 0) wave_sum[wid] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int k = 0; k < waves; ++k) s += wave_sum[k];
+    *loss = s;
   }
 }
 
@@ -131,6 +147,7 @@ std::vector<at::Tensor> ce_fwd(const at::Tensor& logits, const at::Tensor& label
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int waves = 4;
   int grid = std::max(1, std::min((B + waves - 1) / waves, 1024));
+  if (B <= 256) grid = 1;  // fixed-order in-block sum (see ce_fwd_kernel)
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(grid), dim3(64 * waves), 0, stream,
                      logits.data_ptr<float>(), labels.data_ptr<int64_t>(),
                      probs.data_ptr<float>(), loss.data_ptr<float>(), B, C);

@@ -315,9 +315,11 @@ constexpr int WF_ULD = WF_CO + 1;   // U_lds[f][ci][co]
 constexpr int WF_VLD = WF_T + 1;    // V_lds[f][ci][t]
 
 // ci_per: the ci-range length per grid.z slice.  The output transform is
-// LINEAR in M, so slices transform their PARTIAL sums and atomicAdd into a
-// zeroed y — this fills the chip for small-T/high-Ci shapes whose natural
-// grid is far below one block per CU.  Slice 0 adds the bias.
+// LINEAR in M, so slices transform their PARTIAL sums, each into its own
+// slab of y (y + blockIdx.z * B*Co*OH*OW), reduced in fixed order by
+// wino_slab_reduce_kernel — this fills the chip for small-T/high-Ci shapes
+// whose natural grid is far below one block per CU, and unlike atomicAdd
+// gives the same sum every run.  Slice 0 adds the bias.
 template <bool FLIP>
 __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     const float* __restrict__ x, const float* __restrict__ w,
@@ -326,7 +328,6 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     int ci_per, int CW, FastDiv d_thw, FastDiv d_tw) {
   const int ci_begin = blockIdx.z * ci_per;
   const int ci_end = min(Ci, ci_begin + ci_per);
-  const bool accumulate = gridDim.z > 1;
   // single-buffer two-barrier loop: double buffering would cost 67.6 KB of
   // LDS (2 blocks/CU); at 33.8 KB four blocks fit and the long 32-MFMA
   // phase gives co-resident waves the latency cover instead
@@ -472,22 +473,16 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     const unsigned rem = d_thw.mod((unsigned)t, b);
     const unsigned th = d_tw.div(rem);
     const unsigned tw = d_tw.mod(rem, th);
-    float* yp = y + ((long)b * Co + co) * OH * OW + (long)th * 2 * OW + tw * 2;
+    float* yp = y + (long)blockIdx.z * B * Co * OH * OW +
+                ((long)b * Co + co) * OH * OW + (long)th * 2 * OW + tw * 2;
     const float o00 = u0[0] + u0[1] + u0[2] + bv;
     const float o01 = u0[1] - u0[2] - u0[3] + bv;
     const float o10 = u1[0] + u1[1] + u1[2] + bv;
     const float o11 = u1[1] - u1[2] - u1[3] + bv;
-    if (accumulate) {
-      atomicAdd(&yp[0], o00);
-      atomicAdd(&yp[1], o01);
-      atomicAdd(&yp[OW], o10);
-      atomicAdd(&yp[OW + 1], o11);
-    } else {
-      yp[0] = o00;
-      yp[1] = o01;
-      yp[OW] = o10;
-      yp[OW + 1] = o11;
-    }
+    yp[0] = o00;
+    yp[1] = o01;
+    yp[OW] = o10;
+    yp[OW + 1] = o11;
   }
 }
 
@@ -772,8 +767,8 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
   // staging step) — no wt launch, no 16*Co*Ci frequency tensor
   const int CW = (int)w.size(1);
   // ci-split so the grid reaches ~1 block/CU (output transform is linear in
-  // M: slices atomicAdd partial y tiles; slice count keeps ci chunks at
-  // multiples of the CK=8 step)
+  // M: slices store partial y tiles into per-slice slabs; slice count keeps
+  // ci chunks at multiples of the CK=8 step)
   const long base_blocks = (long)(T / 32) * (Co / 32);
   int splits = 1;
   if (base_blocks < 256) {
@@ -784,13 +779,12 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
   int ci_per = ((Ci / splits + WF_CK - 1) / WF_CK) * WF_CK;
   splits = (Ci + ci_per - 1) / ci_per;
 
-  at::Tensor y;
-  if (splits > 1) {
-    y = at::empty({B, Co, OH, OW}, x.options());
-    slk_zero_async(y.data_ptr<float>(), y.numel(), stream);
-  } else {
-    y = at::empty({B, Co, OH, OW}, x.options());
-  }
+  // every slice covers a non-empty ci range and T, Co are tile multiples, so
+  // each slab is written in full
+  auto y = at::empty({B, Co, OH, OW}, x.options());
+  at::Tensor slab;
+  if (splits > 1) slab = at::empty({splits, B, Co, OH, OW}, x.options());
+  float* yw = splits > 1 ? slab.data_ptr<float>() : y.data_ptr<float>();
   FastDiv d_thw, d_tw;
   d_thw.init(tH * tW);
   d_tw.init(tW);
@@ -799,14 +793,21 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
     hipLaunchKernelGGL(wino_fused_kernel<true>, grid, dim3(256), 0, stream,
                        xc.data_ptr<float>(), wc.data_ptr<float>(),
                        bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                       y.data_ptr<float>(), B, Ci, H, W, Co, OH, OW, tH, tW,
+                       yw, B, Ci, H, W, Co, OH, OW, tH, tW,
                        pad, ci_per, CW, d_thw, d_tw);
   } else {
     hipLaunchKernelGGL(wino_fused_kernel<false>, grid, dim3(256), 0, stream,
                        xc.data_ptr<float>(), wc.data_ptr<float>(),
                        bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                       y.data_ptr<float>(), B, Ci, H, W, Co, OH, OW, tH, tW,
+                       yw, B, Ci, H, W, Co, OH, OW, tH, tW,
                        pad, ci_per, CW, d_thw, d_tw);
+  }
+  if (splits > 1) {
+    const long numel = y.numel();
+    const int rgrid = (int)std::min<long>((numel + 255) / 256, 4096);
+    hipLaunchKernelGGL(wino_slab_reduce_kernel, dim3(rgrid), dim3(256), 0,
+                       stream, slab.data_ptr<float>(), splits,
+                       y.data_ptr<float>(), numel);
   }
   return y;
 }

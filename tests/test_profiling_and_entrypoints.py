@@ -1,6 +1,7 @@
 """Profiler subsystem + entrypoint plumbing tests (CPU)."""
 
 import json
+import os
 import subprocess
 import sys
 
@@ -9,6 +10,8 @@ import torch
 from split_learning_amd.models import get_model_class
 from split_learning_amd.profiling import profile_model, write_profiling_json
 from split_learning_amd.parallel.partition import partition
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_profile_model_vgg16():
@@ -36,7 +39,7 @@ def test_profiling_cli(tmp_path):
     out = tmp_path / "profiling.json"
     r = subprocess.run([sys.executable, "profiling.py", "--model", "ViT",
                        "--size", "2", "--out", str(out)],
-                       capture_output=True, text=True, timeout=300)
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     prof = json.load(open(out))
     assert len(prof["exe_time"]) == 12
