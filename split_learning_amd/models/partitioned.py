@@ -66,7 +66,11 @@ class SequentialUnits(PartitionedModel):
         # still split the pair, in which case both run standalone); a Conv2d
         # feeding a training-mode BatchNorm skips its bias-gradient reduction
         # (analytically zero through batch normalisation — ops/functional.py)
-        from ..ops.modules import HipBatchNorm2d, HipConv2d, HipReLU
+        # A BatchNorm2d -> ReLU -> MaxPool2d(2,2) triple inside one partition
+        # runs as one op in training mode (ops.modules.can_fuse_bn_relu_pool);
+        # a cut that splits the triple leaves the pair rule above.
+        from ..ops.modules import (HipBatchNorm2d, HipConv2d, HipReLU,
+                                   can_fuse_bn_relu_pool)
         units = self.active_units()
         n = len(units)
         i = 0
@@ -75,6 +79,11 @@ class SequentialUnits(PartitionedModel):
             nxt = getattr(self, f"layer{units[i + 1]}") if i + 1 < n else None
             if (isinstance(mod, HipBatchNorm2d) and x.is_cuda
                     and isinstance(nxt, HipReLU)):
+                nxt2 = getattr(self, f"layer{units[i + 2]}") if i + 2 < n else None
+                if can_fuse_bn_relu_pool(mod, nxt2, x):
+                    x = mod(x, fuse_relu=True, fuse_pool=True)
+                    i += 3
+                    continue
                 x = mod(x, fuse_relu=True)
                 i += 2
                 continue

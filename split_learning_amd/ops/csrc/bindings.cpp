@@ -35,6 +35,16 @@ std::vector<at::Tensor> bn2d_bwd(const at::Tensor&, const at::Tensor&,
 std::vector<at::Tensor> bn2d_bwd_eval(const at::Tensor&, const at::Tensor&,
                                       const at::Tensor&, const at::Tensor&,
                                       const at::Tensor&, c10::optional<at::Tensor>);
+std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&,
+                                       c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>, double, double,
+                                       bool, bool);
+std::vector<at::Tensor> bn2d_train_bwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>);
 std::vector<at::Tensor> drop_res_ln_fwd(const at::Tensor&, const at::Tensor&,
                                         const at::Tensor&, const at::Tensor&,
                                         double, double, int64_t,
@@ -116,6 +126,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn2d_bwd_eval", &slk::bn2d_bwd_eval, py::arg("x"), py::arg("gy"),
         py::arg("gamma"), py::arg("mean"), py::arg("invstd"),
         py::arg("relu_y") = py::none());
+  m.def("bn2d_train_fwd", &slk::bn2d_train_fwd, py::arg("x"), py::arg("gamma"),
+        py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"),
+        py::arg("relu") = false, py::arg("pool") = false);
+  m.def("bn2d_train_bwd", &slk::bn2d_train_bwd, py::arg("x"), py::arg("gy"),
+        py::arg("gamma"), py::arg("mean"), py::arg("invstd"),
+        py::arg("relu_y") = py::none(), py::arg("idx") = py::none());
   m.def("drop_res_ln_fwd", &slk::drop_res_ln_fwd, py::arg("x"), py::arg("res"),
         py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p") = 0.0,
         py::arg("seed") = 0, py::arg("offset") = py::none());

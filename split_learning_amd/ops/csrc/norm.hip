@@ -23,10 +23,138 @@ static inline at::Tensor zeroed(at::IntArrayRef sizes, const at::TensorOptions& 
 
 // ---------------- BatchNorm2d ----------------
 
-// chunked partial sums (grid.y chunks per channel -> float atomics) followed
-// by a finalize kernel that also folds invstd and the running-stat update
-// in-kernel (the previous host-side rsqrt/mul_/add_ chain was 5 extra
-// kernel launches per BN call).
+// Per-element expressions shared by every BN kernel below (chunked, one-
+// kernel, pooled): one definition each, so the separate-launch and the
+// single-launch forms of a layer compute bit-identical values.  Contraction
+// is spelled out rather than left to the compiler: where a block holds a
+// channel's sums as loop invariants it hoisted sum_gy * inv_n and fused the
+// OTHER product instead, a last-bit difference from the per-element kernels
+// whenever 1/n is not a power of two.  The explicit forms are the ones the
+// per-element kernels (bn_fwd_kernel, bn_bwd_dx_kernel) have always compiled
+// to: y = fma(xhat, gamma, beta); dx = gamma*is*(fma(-inv_n, sum_gy, g) -
+// xhat*sum_gy_xhat*inv_n).
+__device__ __forceinline__ float bn_apply(float xv, float m, float is, float g,
+                                          float b, bool relu) {
+#pragma clang fp contract(off)
+  float v = __builtin_fmaf((xv - m) * is, g, b);
+  if (relu) v = fmaxf(v, 0.f);
+  return v;
+}
+
+__device__ __forceinline__ float bn_dx(float xv, float g, float m, float is,
+                                       float gamma, float sum_gy,
+                                       float sum_gy_xhat, float inv_n) {
+#pragma clang fp contract(off)
+  const float xhat = (xv - m) * is;
+  const float t = __builtin_fmaf(-inv_n, sum_gy, g);
+  return gamma * is * (t - xhat * sum_gy_xhat * inv_n);
+}
+
+// Geometry of the MaxPool2d(2,2) folded behind BN+ReLU (H and W even):
+// W is the full-resolution row length, OH x OW the pooled plane.
+struct PoolGeom {
+  int W, OH, OW;
+  FastDiv d_w, d_ow, d_ohow;
+};
+
+static inline PoolGeom pool_geom(int H, int W) {
+  PoolGeom pg;
+  pg.W = W;
+  pg.OH = H / 2;
+  pg.OW = W / 2;
+  pg.d_w.init(W);
+  pg.d_ow.init(pg.OW);
+  pg.d_ohow.init(pg.OH * pg.OW);
+  return pg;
+}
+
+// BN+ReLU of the 2x2 window at xp, then maxpool_fwd_kernel's selection rule:
+// start from position 0, replace on strict > in the order 1, 2, 3.
+__device__ __forceinline__ float bn_relu_pool_window(const float* __restrict__ xp,
+                                                     int W, float m, float is,
+                                                     float g, float b, int& bi) {
+  float best = bn_apply(xp[0], m, is, g, b, true);
+  bi = 0;
+  float v = bn_apply(xp[1], m, is, g, b, true);
+  if (v > best) { best = v; bi = 1; }
+  v = bn_apply(xp[W], m, is, g, b, true);
+  if (v > best) { best = v; bi = 2; }
+  v = bn_apply(xp[W + 1], m, is, g, b, true);
+  if (v > best) { best = v; bi = 3; }
+  return best;
+}
+
+// Gradient arriving at full-resolution element (bc, r), r = h*W + w.
+// !POOL: gy/relu_y are full resolution; relu_y != nullptr fuses the ReLU
+// backward mask (g = y>0 ? gy : 0).  POOL: gy, relu_y (the pooled output) and
+// idx are at pooled resolution — the element gets the pooled gradient iff it
+// was the window's argmax and the pooled value passed the ReLU, which is what
+// maxpool_bwd followed by the full-resolution mask yields.  The test is
+// !(y <= 0) so a NaN behaves as in the full-resolution mask.
+template <bool POOL>
+__device__ __forceinline__ float bn_gy_at(const float* __restrict__ gy,
+                                          const float* __restrict__ relu_y,
+                                          const uint8_t* __restrict__ idx,
+                                          long off, unsigned bc, unsigned r,
+                                          const PoolGeom& pg) {
+  if (POOL) {
+    const unsigned h = pg.d_w.div(r);
+    const unsigned w = pg.d_w.mod(r, h);
+    const long o = ((long)bc * pg.OH + (h >> 1)) * pg.OW + (w >> 1);
+    const unsigned pos = ((h & 1) << 1) | (w & 1);
+    return (idx[o] == (uint8_t)pos && !(relu_y[o] <= 0.f)) ? gy[o] : 0.f;
+  } else {
+    float g = gy[off];
+    if (relu_y != nullptr && relu_y[off] <= 0.f) g = 0.f;
+    return g;
+  }
+}
+
+// sum(x) and sum(x^2) of channel c over the linear (b, hw) range [lo, hi):
+// thread t accumulates lo+t, lo+t+blockDim, ... in double, then the block
+// sum.  Result valid in thread 0.
+__device__ __forceinline__ void bn_stat_sums(const float* __restrict__ x, int c,
+                                             int lo, int hi, int C, int HW,
+                                             const FastDiv& d_hw, double* scratch,
+                                             double& ts, double& ts2) {
+  double s = 0.0, s2 = 0.0;
+  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    // FastDiv: the plain i / HW was a ~25-VALU runtime division PER ELEMENT
+    const unsigned b = d_hw.div((unsigned)i);
+    const unsigned r = d_hw.mod((unsigned)i, b);
+    const double v = (double)x[((long)b * C + c) * HW + r];
+    s += v;
+    s2 += v * v;
+  }
+  ts = slk_block_sum(s, scratch);
+  __syncthreads();
+  ts2 = slk_block_sum(s2, scratch);
+}
+
+// mean / invstd / running-stat update of one channel from its float sums
+__device__ __forceinline__ void bn_finalize_channel(
+    float s, float s2, float n, int c, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float momentum, float eps, float& m_out,
+    float& is_out) {
+  const float m = s / n;
+  const float v = fmaxf(s2 / n - m * m, 0.f);
+  const float is = rsqrtf(v + eps);
+  mean[c] = m;
+  invstd[c] = is;
+  if (running_mean != nullptr) {
+    const float unbiased = v * (n / fmaxf(n - 1.f, 1.f));
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  }
+  m_out = m;
+  is_out = is;
+}
+
+// chunked partial sums (grid.y chunks per channel) followed by a finalize
+// kernel that also folds invstd and the running-stat update in-kernel (the
+// previous host-side rsqrt/mul_/add_ chain was 5 extra kernel launches per
+// BN call).
 // slab layout [2][chunks][C]: every slot plainly written (no zero-init, no
 // atomics); the finalize kernel reduces over chunks
 __global__ void bn_partial_kernel(const float* __restrict__ x,
@@ -38,18 +166,8 @@ __global__ void bn_partial_kernel(const float* __restrict__ x,
   const int per = (total + gridDim.y - 1) / gridDim.y;
   const int lo = blockIdx.y * per;
   const int hi = min(total, lo + per);
-  double s = 0.0, s2 = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    // FastDiv: the plain i / HW was a ~25-VALU runtime division PER ELEMENT
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const double v = (double)x[((long)b * C + c) * HW + r];
-    s += v;
-    s2 += v * v;
-  }
-  double ts = slk_block_sum(s, scratch);
-  __syncthreads();
-  double ts2 = slk_block_sum(s2, scratch);
+  double ts, ts2;
+  bn_stat_sums(x, c, lo, hi, C, HW, d_hw, scratch, ts, ts2);
   if (threadIdx.x == 0) {
     const long chunks = gridDim.y;
     slab[(long)blockIdx.y * C + c] = (float)ts;
@@ -73,15 +191,9 @@ __global__ void bn_finalize_kernel(const float* __restrict__ slab, int chunks,
     s += slab[(long)k * C + c];
     s2 += slab[(long)chunks * C + (long)k * C + c];
   }
-  const float m = s / n;
-  const float v = fmaxf(s2 / n - m * m, 0.f);
-  mean[c] = m;
-  invstd[c] = rsqrtf(v + eps);
-  if (running_mean != nullptr) {
-    const float unbiased = v * (n / fmaxf(n - 1.f, 1.f));
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
+  float m, is;
+  bn_finalize_channel(s, s2, n, c, mean, invstd, running_mean, running_var,
+                      momentum, eps, m, is);
 }
 
 // chunks==1 (B*HW <= 8191: the 8x8-and-smaller VGG layers at B=32): ONE
@@ -100,27 +212,68 @@ __global__ void bn_stats_one_kernel(const float* __restrict__ x,
   const int c = blockIdx.x;
   if (c == 0 && threadIdx.x == 0 && nbt != nullptr) nbt[0] += 1;
   const int total = B * HW;
-  double s = 0.0, s2 = 0.0;
-  for (int i = threadIdx.x; i < total; i += blockDim.x) {
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const double v = (double)x[((long)b * C + c) * HW + r];
-    s += v;
-    s2 += v * v;
-  }
-  double ts = slk_block_sum(s, scratch);
-  __syncthreads();
-  double ts2 = slk_block_sum(s2, scratch);
+  double ts, ts2;
+  bn_stat_sums(x, c, 0, total, C, HW, d_hw, scratch, ts, ts2);
   if (threadIdx.x == 0) {
-    const float n = (float)total;
-    const float m = (float)ts / n;
-    const float v = fmaxf((float)ts2 / n - m * m, 0.f);
-    mean[c] = m;
-    invstd[c] = rsqrtf(v + eps);
-    if (running_mean != nullptr) {
-      const float unbiased = v * (n / fmaxf(n - 1.f, 1.f));
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+    float m, is;
+    bn_finalize_channel((float)ts, (float)ts2, (float)total, c, mean, invstd,
+                        running_mean, running_var, momentum, eps, m, is);
+  }
+}
+
+// Single-launch training forward for chunks==1: phase 1 is
+// bn_stats_one_kernel; phase 2 applies the result to the channel the block
+// has just reduced (re-read from cache: at most 8191 floats) and writes y,
+// or — POOL — the 2x2-pooled y and its argmax index, one thread per pooled
+// output, with no full-resolution y at all.
+template <bool POOL>
+__global__ void bn_fwd_one_kernel(const float* __restrict__ x,
+                                  float* __restrict__ y,
+                                  uint8_t* __restrict__ idx,
+                                  float* __restrict__ mean,
+                                  float* __restrict__ invstd,
+                                  float* __restrict__ running_mean,
+                                  float* __restrict__ running_var,
+                                  long* __restrict__ nbt,
+                                  const float* __restrict__ gamma,
+                                  const float* __restrict__ beta, int B, int C,
+                                  int HW, float momentum, float eps, bool relu,
+                                  FastDiv d_hw, PoolGeom pg) {
+  __shared__ double scratch[16];
+  __shared__ float s_stat[2];
+  const int c = blockIdx.x;
+  if (c == 0 && threadIdx.x == 0 && nbt != nullptr) nbt[0] += 1;
+  const int total = B * HW;
+  double ts, ts2;
+  bn_stat_sums(x, c, 0, total, C, HW, d_hw, scratch, ts, ts2);
+  if (threadIdx.x == 0) {
+    bn_finalize_channel((float)ts, (float)ts2, (float)total, c, mean, invstd,
+                        running_mean, running_var, momentum, eps, s_stat[0],
+                        s_stat[1]);
+  }
+  __syncthreads();
+  const float m = s_stat[0], is = s_stat[1], g = gamma[c], bt = beta[c];
+  if (POOL) {
+    const int ohow = pg.OH * pg.OW;
+    const int ptotal = B * ohow;
+    for (int j = threadIdx.x; j < ptotal; j += blockDim.x) {
+      const unsigned b = pg.d_ohow.div((unsigned)j);
+      const unsigned rem = pg.d_ohow.mod((unsigned)j, b);
+      const unsigned oh = pg.d_ow.div(rem);
+      const unsigned ow = pg.d_ow.mod(rem, oh);
+      const long bc = (long)b * C + c;
+      const float* xp = x + bc * HW + (long)(oh * 2) * pg.W + ow * 2;
+      int bi;
+      const float best = bn_relu_pool_window(xp, pg.W, m, is, g, bt, bi);
+      y[bc * ohow + rem] = best;
+      idx[bc * ohow + rem] = (uint8_t)bi;
+    }
+  } else {
+    for (int i = threadIdx.x; i < total; i += blockDim.x) {
+      const unsigned b = d_hw.div((unsigned)i);
+      const unsigned r = d_hw.mod((unsigned)i, b);
+      const long off = ((long)b * C + c) * HW + r;
+      y[off] = bn_apply(x[off], m, is, g, bt, relu);
     }
   }
 }
@@ -135,46 +288,81 @@ __global__ void bn_fwd_kernel(const float* __restrict__ x, float* __restrict__ y
        i += (long)gridDim.x * blockDim.x) {
     const unsigned bc = d_hw.div((unsigned)i);
     const int c = (int)(bc - d_c.div(bc) * (unsigned)C);
-    float v = (x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (relu) v = fmaxf(v, 0.f);
-    y[i] = v;
+    y[i] = bn_apply(x[i], mean[c], invstd[c], gamma[c], beta[c], relu);
   }
 }
 
-// reductions for backward: sum(gy) and sum(gy * xhat) per channel, chunked
-// over grid.y like the forward stats (one block per channel leaves most CUs
-// idle at C=64)
-// relu_y != nullptr fuses the preceding ReLU's backward mask (g = y>0 ? gy
-// : 0) into the reduction — the standalone relu_bwd launch and its full
-// read+write pass disappear from the BN+ReLU block backward.
-__global__ void bn_bwd_reduce_kernel(const float* __restrict__ x,
-                                     const float* __restrict__ gy,
-                                     const float* __restrict__ relu_y,
-                                     const float* __restrict__ mean,
-                                     const float* __restrict__ invstd,
-                                     float* __restrict__ slab, int B, int C,
-                                     int HW, FastDiv d_hw) {
-  __shared__ double scratch[16];
-  const int c = blockIdx.x;
-  const float m = mean[c], is = invstd[c];
-  const int total = B * HW;
-  const int per = (total + gridDim.y - 1) / gridDim.y;
-  const int lo = blockIdx.y * per;
-  const int hi = min(total, lo + per);
+// chunked-stats layers with a pool behind them: BN+ReLU+MaxPool apply, one
+// thread per POOLED output (ptotal = B*C*OH*OW); writes pooled y + argmax
+__global__ void bn_pool_fwd_kernel(const float* __restrict__ x,
+                                   float* __restrict__ y,
+                                   uint8_t* __restrict__ idx,
+                                   const float* __restrict__ mean,
+                                   const float* __restrict__ invstd,
+                                   const float* __restrict__ gamma,
+                                   const float* __restrict__ beta, long ptotal,
+                                   int C, int HW, PoolGeom pg, FastDiv d_c) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < ptotal;
+       i += (long)gridDim.x * blockDim.x) {
+    const unsigned bc = pg.d_ohow.div((unsigned)i);
+    const unsigned rem = pg.d_ohow.mod((unsigned)i, bc);
+    const unsigned oh = pg.d_ow.div(rem);
+    const unsigned ow = pg.d_ow.mod(rem, oh);
+    const int c = (int)(bc - d_c.div(bc) * (unsigned)C);
+    const float* xp = x + (long)bc * HW + (long)(oh * 2) * pg.W + ow * 2;
+    int bi;
+    y[i] = bn_relu_pool_window(xp, pg.W, mean[c], invstd[c], gamma[c], beta[c],
+                               bi);
+    idx[i] = (uint8_t)bi;
+  }
+}
+
+// reductions for backward: sum(gy) and sum(gy * xhat) of channel c over the
+// linear (b, hw) range [lo, hi), same per-thread order as bn_stat_sums.
+// The incoming gradient is fetched through bn_gy_at, so the preceding ReLU's
+// mask (and, POOL, the max-pool scatter) ride inside the reduction — no
+// standalone relu_bwd / maxpool_bwd launch, no extra full tensor pass.
+template <bool POOL>
+__device__ __forceinline__ void bn_bwd_sums(
+    const float* __restrict__ x, const float* __restrict__ gy,
+    const float* __restrict__ relu_y, const uint8_t* __restrict__ idx, float m,
+    float is, int c, int lo, int hi, int C, int HW, const FastDiv& d_hw,
+    const PoolGeom& pg, double* scratch, double& ts, double& tsx) {
   double s = 0.0, sx = 0.0;
   for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     const unsigned b = d_hw.div((unsigned)i);
     const unsigned r = d_hw.mod((unsigned)i, b);
-    const long off = ((long)b * C + c) * HW + r;
-    float gf = gy[off];
-    if (relu_y != nullptr && relu_y[off] <= 0.f) gf = 0.f;
-    const double g = (double)gf;
+    const unsigned bc = b * (unsigned)C + c;
+    const long off = (long)bc * HW + r;
+    const double g = (double)bn_gy_at<POOL>(gy, relu_y, idx, off, bc, r, pg);
     s += g;
     sx += g * (double)((x[off] - m) * is);
   }
-  double ts = slk_block_sum(s, scratch);
+  ts = slk_block_sum(s, scratch);
   __syncthreads();
-  double tsx = slk_block_sum(sx, scratch);
+  tsx = slk_block_sum(sx, scratch);
+}
+
+// chunked over grid.y like the forward stats (one block per channel leaves
+// most CUs idle at C=64)
+template <bool POOL>
+__global__ void bn_bwd_reduce_kernel(const float* __restrict__ x,
+                                     const float* __restrict__ gy,
+                                     const float* __restrict__ relu_y,
+                                     const uint8_t* __restrict__ idx,
+                                     const float* __restrict__ mean,
+                                     const float* __restrict__ invstd,
+                                     float* __restrict__ slab, int B, int C,
+                                     int HW, FastDiv d_hw, PoolGeom pg) {
+  __shared__ double scratch[16];
+  const int c = blockIdx.x;
+  const int total = B * HW;
+  const int per = (total + gridDim.y - 1) / gridDim.y;
+  const int lo = blockIdx.y * per;
+  const int hi = min(total, lo + per);
+  double ts, tsx;
+  bn_bwd_sums<POOL>(x, gy, relu_y, idx, mean[c], invstd[c], c, lo, hi, C, HW,
+                    d_hw, pg, scratch, ts, tsx);
   if (threadIdx.x == 0) {
     const long chunks = gridDim.y;
     slab[(long)blockIdx.y * C + c] = (float)ts;
@@ -194,25 +382,53 @@ __global__ void bn_bwd_reduce_one_kernel(const float* __restrict__ x,
                                          int B, int C, int HW, FastDiv d_hw) {
   __shared__ double scratch[16];
   const int c = blockIdx.x;
-  const float m = mean[c], is = invstd[c];
-  const int total = B * HW;
-  double s = 0.0, sx = 0.0;
-  for (int i = threadIdx.x; i < total; i += blockDim.x) {
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const long off = ((long)b * C + c) * HW + r;
-    float gf = gy[off];
-    if (relu_y != nullptr && relu_y[off] <= 0.f) gf = 0.f;
-    const double g = (double)gf;
-    s += g;
-    sx += g * (double)((x[off] - m) * is);
-  }
-  double ts = slk_block_sum(s, scratch);
-  __syncthreads();
-  double tsx = slk_block_sum(sx, scratch);
+  double ts, tsx;
+  bn_bwd_sums<false>(x, gy, relu_y, nullptr, mean[c], invstd[c], c, 0, B * HW,
+                     C, HW, d_hw, PoolGeom{}, scratch, ts, tsx);
   if (threadIdx.x == 0) {
     sum_gy[c] = (float)ts;
     sum_gy_xhat[c] = (float)tsx;
+  }
+}
+
+// Single-launch training backward for chunks==1: phase 1 is
+// bn_bwd_reduce_one_kernel, phase 2 the bn_bwd_dx math for the channel the
+// block has just reduced.  Writes gx and the two sums (ggamma, gbeta).
+template <bool POOL>
+__global__ void bn_bwd_one_kernel(const float* __restrict__ x,
+                                  const float* __restrict__ gy,
+                                  const float* __restrict__ relu_y,
+                                  const uint8_t* __restrict__ idx,
+                                  const float* __restrict__ mean,
+                                  const float* __restrict__ invstd,
+                                  const float* __restrict__ gamma,
+                                  float* __restrict__ sum_gy,
+                                  float* __restrict__ sum_gy_xhat,
+                                  float* __restrict__ gx, int B, int C, int HW,
+                                  float inv_n, FastDiv d_hw, PoolGeom pg) {
+  __shared__ double scratch[16];
+  __shared__ float s_sum[2];
+  const int c = blockIdx.x;
+  const float m = mean[c], is = invstd[c];
+  const int total = B * HW;
+  double ts, tsx;
+  bn_bwd_sums<POOL>(x, gy, relu_y, idx, m, is, c, 0, total, C, HW, d_hw, pg,
+                    scratch, ts, tsx);
+  if (threadIdx.x == 0) {
+    s_sum[0] = (float)ts;
+    s_sum[1] = (float)tsx;
+    sum_gy[c] = (float)ts;
+    sum_gy_xhat[c] = (float)tsx;
+  }
+  __syncthreads();
+  const float sgy = s_sum[0], sgx = s_sum[1], gm = gamma[c];
+  for (int i = threadIdx.x; i < total; i += blockDim.x) {
+    const unsigned b = d_hw.div((unsigned)i);
+    const unsigned r = d_hw.mod((unsigned)i, b);
+    const unsigned bc = b * (unsigned)C + c;
+    const long off = (long)bc * HW + r;
+    const float g = bn_gy_at<POOL>(gy, relu_y, idx, off, bc, r, pg);
+    gx[off] = bn_dx(x[off], g, m, is, gm, sgy, sgx, inv_n);
   }
 }
 
@@ -230,9 +446,11 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ slab, int chunk
   sum_gy_xhat[c] = sx;
 }
 
+template <bool POOL>
 __global__ void bn_bwd_dx_kernel(const float* __restrict__ x,
                                  const float* __restrict__ gy,
                                  const float* __restrict__ relu_y,
+                                 const uint8_t* __restrict__ idx,
                                  const float* __restrict__ mean,
                                  const float* __restrict__ invstd,
                                  const float* __restrict__ gamma,
@@ -240,18 +458,17 @@ __global__ void bn_bwd_dx_kernel(const float* __restrict__ x,
                                  const float* __restrict__ sum_gy_xhat,
                                  float* __restrict__ gx, long total, int C, int HW,
                                  float inv_n, bool training, FastDiv d_hw,
-                                 FastDiv d_c) {
+                                 FastDiv d_c, PoolGeom pg) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
     const unsigned bc = d_hw.div((unsigned)i);
+    const unsigned r = d_hw.mod((unsigned)i, bc);
     const int c = (int)(bc - d_c.div(bc) * (unsigned)C);
     const float is = invstd[c];
-    float g = gy[i];
-    if (relu_y != nullptr && relu_y[i] <= 0.f) g = 0.f;
+    const float g = bn_gy_at<POOL>(gy, relu_y, idx, i, bc, r, pg);
     if (training) {
-      const float xhat = (x[i] - mean[c]) * is;
-      gx[i] = gamma[c] * is *
-              (g - sum_gy[c] * inv_n - xhat * sum_gy_xhat[c] * inv_n);
+      gx[i] = bn_dx(x[i], g, mean[c], is, gamma[c], sum_gy[c], sum_gy_xhat[c],
+                    inv_n);
     } else {
       gx[i] = g * gamma[c] * is;
     }
@@ -263,6 +480,11 @@ static inline int bn_chunks(long per_channel) {
   if (c < 1) c = 1;
   if (c > 16) c = 16;
   return (int)c;
+}
+
+template <typename T>
+static inline T* opt_ptr(const c10::optional<at::Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 
 std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
@@ -280,13 +502,9 @@ std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
   if (chunks == 1) {
     hipLaunchKernelGGL(bn_stats_one_kernel, dim3(C), dim3(256), 0, stream,
                        x.data_ptr<float>(), mean.data_ptr<float>(),
-                       invstd.data_ptr<float>(),
-                       running_mean.has_value() ? running_mean->data_ptr<float>()
-                                                : nullptr,
-                       running_var.has_value() ? running_var->data_ptr<float>()
-                                               : nullptr,
-                       num_batches_tracked.has_value()
-                           ? num_batches_tracked->data_ptr<long>() : nullptr,
+                       invstd.data_ptr<float>(), opt_ptr<float>(running_mean),
+                       opt_ptr<float>(running_var),
+                       opt_ptr<long>(num_batches_tracked),
                        B, C, HW, (float)momentum, (float)eps, d_hw);
     return {mean, invstd};
   }
@@ -297,12 +515,8 @@ std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
                      stream, slab.data_ptr<float>(), chunks,
                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     running_mean.has_value() ? running_mean->data_ptr<float>()
-                                              : nullptr,
-                     running_var.has_value() ? running_var->data_ptr<float>()
-                                             : nullptr,
-                     num_batches_tracked.has_value()
-                         ? num_batches_tracked->data_ptr<long>() : nullptr,
+                     opt_ptr<float>(running_mean), opt_ptr<float>(running_var),
+                     opt_ptr<long>(num_batches_tracked),
                      C, (float)((long)B * HW), (float)momentum, (float)eps);
   return {mean, invstd};
 }
@@ -327,48 +541,151 @@ at::Tensor bn2d_fwd(const at::Tensor& x, const at::Tensor& mean,
   return y;
 }
 
+// Training-mode forward of a whole BN block: statistics + running-stat update
+// + apply (+ReLU) (+MaxPool 2x2).  chunks==1 layers run as ONE launch; larger
+// layers keep the chunked statistics and get one apply launch.  With pool the
+// output is the pooled y plus its uint8 argmax; no full-resolution y exists.
+// Returns {y, mean, invstd} or {y, mean, invstd, idx}.
+std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor& x, const at::Tensor& gamma,
+                                       const at::Tensor& beta,
+                                       c10::optional<at::Tensor> running_mean,
+                                       c10::optional<at::Tensor> running_var,
+                                       c10::optional<at::Tensor> num_batches_tracked,
+                                       double momentum, double eps, bool relu,
+                                       bool pool) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous() &&
+              x.scalar_type() == at::kFloat, "bn2d_train_fwd: x");
+  const int B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int HW = H * W;
+  TORCH_CHECK(x.numel() <= (1l << 24), "bn2d_train_fwd: FastDiv range");
+  TORCH_CHECK(!pool || (relu && H % 2 == 0 && W % 2 == 0 && HW > 0),
+              "bn2d_train_fwd: pool needs relu and even H, W");
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const PoolGeom pg = pool ? pool_geom(H, W) : PoolGeom{};
+  at::Tensor y, idx;
+  if (pool) {
+    y = at::empty({B, C, H / 2, W / 2}, x.options());
+    idx = at::empty({B, C, H / 2, W / 2}, x.options().dtype(at::kByte));
+  }
+  if (bn_chunks((long)B * HW) == 1) {
+    auto mean = at::empty({C}, x.options());
+    auto invstd = at::empty({C}, x.options());
+    if (!pool) y = at::empty_like(x);
+    FastDiv d_hw;
+    d_hw.init(HW);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(C), dim3(256), 0, stream,
+                         x.data_ptr<float>(), y.data_ptr<float>(),
+                         pool ? idx.data_ptr<uint8_t>() : nullptr,
+                         mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                         opt_ptr<float>(running_mean), opt_ptr<float>(running_var),
+                         opt_ptr<long>(num_batches_tracked),
+                         gamma.data_ptr<float>(), beta.data_ptr<float>(), B, C,
+                         HW, (float)momentum, (float)eps, relu, d_hw, pg);
+    };
+    if (pool) launch(bn_fwd_one_kernel<true>);
+    else launch(bn_fwd_one_kernel<false>);
+    if (pool) return {y, mean, invstd, idx};
+    return {y, mean, invstd};
+  }
+  auto stats = bn2d_stats_fused(x, running_mean, running_var, num_batches_tracked,
+                                momentum, eps);
+  if (!pool) return {bn2d_fwd(x, stats[0], stats[1], gamma, beta, relu), stats[0],
+                     stats[1]};
+  const long ptotal = y.numel();
+  int grid = (int)std::min<long>((ptotal + 255) / 256, 2048);
+  FastDiv d_c;
+  d_c.init(C);
+  hipLaunchKernelGGL(bn_pool_fwd_kernel, dim3(grid), dim3(256), 0, stream,
+                     x.data_ptr<float>(), y.data_ptr<float>(),
+                     idx.data_ptr<uint8_t>(), stats[0].data_ptr<float>(),
+                     stats[1].data_ptr<float>(), gamma.data_ptr<float>(),
+                     beta.data_ptr<float>(), ptotal, C, HW, pg, d_c);
+  return {y, stats[0], stats[1], idx};
+}
+
+// idx given: gy and relu_y are the POOLED gradient / output of a fused
+// BN+ReLU+MaxPool block.  one_launch: chunks==1 training layers run
+// reduce + dx as a single kernel.
 static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tensor& gy,
                                              const at::Tensor& gamma,
                                              const at::Tensor& mean,
                                              const at::Tensor& invstd, bool training,
-                                             const c10::optional<at::Tensor>& relu_y) {
-  const float* ry = relu_y.has_value() ? relu_y->data_ptr<float>() : nullptr;
+                                             const c10::optional<at::Tensor>& relu_y,
+                                             const c10::optional<at::Tensor>& idx,
+                                             bool one_launch) {
+  const float* ry = opt_ptr<float>(relu_y);
+  const bool pool = idx.has_value();
+  const uint8_t* ip = pool ? idx->data_ptr<uint8_t>() : nullptr;
   const int B = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   const long total = x.numel();
+  TORCH_CHECK(total <= (1l << 24), "bn_bwd: FastDiv range");
+  PoolGeom pg{};
+  if (pool) {
+    const int H = x.size(2), W = x.size(3);
+    TORCH_CHECK(training && ry != nullptr && H % 2 == 0 && W % 2 == 0,
+                "bn_bwd: pooled form needs training mode, relu_y and even H, W");
+    TORCH_CHECK(gy.numel() * 4 == total && relu_y->numel() * 4 == total &&
+                idx->numel() * 4 == total, "bn_bwd: pooled operand shapes");
+    pg = pool_geom(H, W);
+  } else {
+    TORCH_CHECK(gy.numel() == total && (ry == nullptr || relu_y->numel() == total),
+                "bn_bwd: operand shapes");
+  }
   auto sum_gy = at::empty({C}, x.options());
   auto sum_gy_xhat = at::empty({C}, x.options());
   auto gx = at::empty_like(x);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int rchunks = bn_chunks((long)B * HW);
+  const float inv_n = 1.0f / (float)((long)B * HW);
   FastDiv d_hw;
   d_hw.init(HW);
-  if (rchunks == 1) {
+  if (rchunks == 1 && one_launch && training) {
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(C), dim3(256), 0, stream,
+                         x.data_ptr<float>(), gy.data_ptr<float>(), ry, ip,
+                         mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                         gamma.data_ptr<float>(), sum_gy.data_ptr<float>(),
+                         sum_gy_xhat.data_ptr<float>(), gx.data_ptr<float>(), B,
+                         C, HW, inv_n, d_hw, pg);
+    };
+    if (pool) launch(bn_bwd_one_kernel<true>);
+    else launch(bn_bwd_one_kernel<false>);
+    return {gx, sum_gy_xhat, sum_gy};
+  }
+  if (rchunks == 1 && !pool) {
     hipLaunchKernelGGL(bn_bwd_reduce_one_kernel, dim3(C), dim3(256), 0, stream,
                        x.data_ptr<float>(), gy.data_ptr<float>(), ry,
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        sum_gy.data_ptr<float>(), sum_gy_xhat.data_ptr<float>(),
                        B, C, HW, d_hw);
   } else {
-  auto slab = at::empty({2, rchunks, C}, x.options());
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, rchunks),
-                     dim3(256), 0, stream,
-                     x.data_ptr<float>(), gy.data_ptr<float>(), ry,
-                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     slab.data_ptr<float>(), B, C, HW, d_hw);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
-                     stream, slab.data_ptr<float>(), rchunks,
-                     sum_gy.data_ptr<float>(), sum_gy_xhat.data_ptr<float>(), C);
+    auto slab = at::empty({2, rchunks, C}, x.options());
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(C, rchunks), dim3(256), 0, stream,
+                         x.data_ptr<float>(), gy.data_ptr<float>(), ry, ip,
+                         mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                         slab.data_ptr<float>(), B, C, HW, d_hw, pg);
+    };
+    if (pool) launch(bn_bwd_reduce_kernel<true>);
+    else launch(bn_bwd_reduce_kernel<false>);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
+                       stream, slab.data_ptr<float>(), rchunks,
+                       sum_gy.data_ptr<float>(), sum_gy_xhat.data_ptr<float>(), C);
   }
   int grid = (int)std::min<long>((total + 255) / 256, 2048);
   FastDiv d_c;
   d_c.init(C);
-  TORCH_CHECK(total <= (1l << 24), "bn_bwd: FastDiv range");
-  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid), dim3(256), 0, stream,
-                     x.data_ptr<float>(), gy.data_ptr<float>(), ry,
-                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     gamma.data_ptr<float>(), sum_gy.data_ptr<float>(),
-                     sum_gy_xhat.data_ptr<float>(), gx.data_ptr<float>(), total, C,
-                     HW, 1.0f / (float)((long)B * HW), training, d_hw, d_c);
+  auto launch_dx = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream,
+                       x.data_ptr<float>(), gy.data_ptr<float>(), ry, ip,
+                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                       gamma.data_ptr<float>(), sum_gy.data_ptr<float>(),
+                       sum_gy_xhat.data_ptr<float>(), gx.data_ptr<float>(), total,
+                       C, HW, inv_n, training, d_hw, d_c, pg);
+  };
+  if (pool) launch_dx(bn_bwd_dx_kernel<true>);
+  else launch_dx(bn_bwd_dx_kernel<false>);
   // ggamma = sum_gy_xhat, gbeta = sum_gy
   return {gx, sum_gy_xhat, sum_gy};
 }
@@ -377,14 +694,29 @@ std::vector<at::Tensor> bn2d_bwd(const at::Tensor& x, const at::Tensor& gy,
                                  const at::Tensor& gamma, const at::Tensor& mean,
                                  const at::Tensor& invstd,
                                  c10::optional<at::Tensor> relu_y) {
-  return bn2d_bwd_impl(x, gy, gamma, mean, invstd, true, relu_y);
+  return bn2d_bwd_impl(x, gy, gamma, mean, invstd, true, relu_y, c10::nullopt,
+                       false);
 }
 
 std::vector<at::Tensor> bn2d_bwd_eval(const at::Tensor& x, const at::Tensor& gy,
                                       const at::Tensor& gamma, const at::Tensor& mean,
                                       const at::Tensor& invstd,
                                       c10::optional<at::Tensor> relu_y) {
-  return bn2d_bwd_impl(x, gy, gamma, mean, invstd, false, relu_y);
+  return bn2d_bwd_impl(x, gy, gamma, mean, invstd, false, relu_y, c10::nullopt,
+                       false);
+}
+
+// Training-mode backward of a whole BN block (the counterpart of
+// bn2d_train_fwd): one launch for chunks==1 layers; with idx, gy and relu_y
+// are pooled and no full-resolution gradient is materialised.
+std::vector<at::Tensor> bn2d_train_bwd(const at::Tensor& x, const at::Tensor& gy,
+                                       const at::Tensor& gamma,
+                                       const at::Tensor& mean,
+                                       const at::Tensor& invstd,
+                                       c10::optional<at::Tensor> relu_y,
+                                       c10::optional<at::Tensor> idx) {
+  TORCH_CHECK(x.is_contiguous() && gy.is_contiguous(), "bn2d_train_bwd: layout");
+  return bn2d_bwd_impl(x, gy, gamma, mean, invstd, true, relu_y, idx, true);
 }
 
 // ---------------- fused transformer epilogue ------------------------------

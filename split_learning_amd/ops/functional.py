@@ -188,22 +188,35 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, bias_grad_zero=False):
 # BatchNorm2d (training + eval), optional fused ReLU
 # ---------------------------------------------------------------------------
 
+# SLK_BN_FUSED=0 restores the separate-launch BN block (stats, apply and pool
+# as their own ops) for same-build A/B and bisection.  Default: training BN
+# layers with chunks == 1 run as one launch per direction, and a
+# BN -> ReLU -> MaxPool2d(2,2) triple runs as one op (BnReluPool2x2Fn).
+BN_FUSED = os.environ.get("SLK_BN_FUSED", "1") != "0"
+
+
 class BatchNorm2dFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps,
                 fuse_relu, num_batches_tracked):
         x = x.contiguous()
-        if training:
-            # fused kernel: batch mean + biased-var invstd + torch-exact
-            # running-stat update (unbiased var) + num_batches_tracked++,
-            # all device-side in one launch pair
-            mean, invstd = native().bn2d_stats_fused(x, running_mean, running_var,
-                                                     num_batches_tracked,
-                                                     momentum, eps)
+        ctx.one_launch = training and BN_FUSED
+        if ctx.one_launch:
+            # batch stats + torch-exact running-stat update (unbiased var) +
+            # num_batches_tracked++ + apply: one launch when a block per
+            # channel covers the layer, chunked stats + apply otherwise
+            y, mean, invstd = native().bn2d_train_fwd(
+                x, gamma, beta, running_mean, running_var, num_batches_tracked,
+                momentum, eps, fuse_relu, False)
         else:
-            mean = running_mean
-            invstd = (running_var + eps).rsqrt()
-        y = native().bn2d_fwd(x, mean, invstd, gamma, beta, fuse_relu)
+            if training:
+                mean, invstd = native().bn2d_stats_fused(
+                    x, running_mean, running_var, num_batches_tracked,
+                    momentum, eps)
+            else:
+                mean = running_mean
+                invstd = (running_var + eps).rsqrt()
+            y = native().bn2d_fwd(x, mean, invstd, gamma, beta, fuse_relu)
         ctx.save_for_backward(x, gamma, mean, invstd, y)
         ctx.training = training
         ctx.fuse_relu = fuse_relu
@@ -216,7 +229,10 @@ class BatchNorm2dFn(Function):
         # fused ReLU backward: the mask rides inside the BN backward kernels
         # (no standalone relu_bwd launch, no extra full tensor pass)
         relu_y = y if ctx.fuse_relu else None
-        if ctx.training:
+        if ctx.one_launch:
+            gx, ggamma, gbeta = native().bn2d_train_bwd(x, gy, gamma, mean,
+                                                        invstd, relu_y, None)
+        elif ctx.training:
             gx, ggamma, gbeta = native().bn2d_bwd(x, gy, gamma, mean, invstd,
                                                   relu_y)
         else:
@@ -230,6 +246,37 @@ def batch_norm2d(x, gamma, beta, running_mean, running_var, training, momentum=0
                  eps=1e-5, fuse_relu=False, num_batches_tracked=None):
     return BatchNorm2dFn.apply(x, gamma, beta, running_mean, running_var, training,
                                momentum, eps, fuse_relu, num_batches_tracked)
+
+
+class BnReluPool2x2Fn(Function):
+    """Training-mode BatchNorm2d -> ReLU -> MaxPool2d(2,2) as one op (even H
+    and W).  Forward writes only the pooled output and its 1-byte argmax;
+    backward derives each full-resolution gradient element from the pooled
+    gradient, the pooled output and the argmax inside the BN backward
+    kernels.  Values are those of the three separate ops, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
+                num_batches_tracked):
+        x = x.contiguous()
+        y, mean, invstd, idx = native().bn2d_train_fwd(
+            x, gamma, beta, running_mean, running_var, num_batches_tracked,
+            momentum, eps, True, True)
+        ctx.save_for_backward(x, gamma, mean, invstd, y, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, mean, invstd, y, idx = ctx.saved_tensors
+        gx, ggamma, gbeta = native().bn2d_train_bwd(x, gy.contiguous(), gamma,
+                                                    mean, invstd, y, idx)
+        return gx, ggamma, gbeta, None, None, None, None, None
+
+
+def bn_relu_maxpool2x2(x, gamma, beta, running_mean, running_var, momentum=0.1,
+                       eps=1e-5, num_batches_tracked=None):
+    return BnReluPool2x2Fn.apply(x, gamma, beta, running_mean, running_var,
+                                 momentum, eps, num_batches_tracked)
 
 
 # ---------------------------------------------------------------------------

@@ -55,17 +55,40 @@ class HipLinear(nn.Linear):
 
 
 class HipBatchNorm2d(nn.BatchNorm2d):
-    def forward(self, x, fuse_relu: bool = False):
+    def forward(self, x, fuse_relu: bool = False, fuse_pool: bool = False):
+        """fuse_pool (callers check can_fuse_bn_relu_pool first) also folds the
+        following ReLU + MaxPool2d(2,2) into the op."""
         if _use_native("bn", x):
             # num_batches_tracked++ happens inside the stats finalize kernel
             nbt = (self.num_batches_tracked
                    if self.training and self.track_running_stats else None)
+            if fuse_pool:
+                return hf.bn_relu_maxpool2x2(x, self.weight, self.bias,
+                                             self.running_mean, self.running_var,
+                                             self.momentum, self.eps,
+                                             num_batches_tracked=nbt)
             return hf.batch_norm2d(x, self.weight, self.bias, self.running_mean,
                                    self.running_var, self.training, self.momentum,
                                    self.eps, fuse_relu=fuse_relu,
                                    num_batches_tracked=nbt)
         y = super().forward(x)
+        if fuse_pool:
+            return F.max_pool2d(torch.relu(y), 2, 2)
         return torch.relu(y) if fuse_relu else y
+
+
+def can_fuse_bn_relu_pool(bn, pool, x: torch.Tensor) -> bool:
+    """True when bn -> HipReLU -> pool on x may run as the single fused op:
+    training-mode BN on the GPU, a plain MaxPool2d(2,2), even H and W, none of
+    the three families routed to torch by SLK_DBG_TORCH, SLK_BN_FUSED not 0."""
+    return (hf.BN_FUSED and x.is_cuda and x.dim() == 4 and bn.training
+            and x.dtype == torch.float32
+            and isinstance(pool, HipMaxPool2d)
+            and pool.kernel_size == 2 and pool.stride == 2
+            and pool.padding == 0 and pool.dilation == 1
+            and not pool.ceil_mode and not pool.return_indices
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.numel() > 0
+            and _DBG_TORCH.isdisjoint(("bn", "relu", "pool")))
 
 
 class HipReLU(nn.ReLU):
