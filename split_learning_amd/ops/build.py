@@ -86,7 +86,8 @@ def build(verbose: bool = True, force: bool = False) -> str:
         sp = os.path.join(CSRC, src)
         op = os.path.join(BUILD_DIR, src.replace("/", "_") + ".o")
         objs.append(op)
-        deps = [sp] + [os.path.join(CSRC, h) for h in ("common.h", "tile_gemm.h")]
+        deps = [sp] + [os.path.join(CSRC, h) for h in (
+            "common.h", "tile_gemm.h", "torch_util.h", "conv_route.h")]
         if (not force and os.path.exists(op)
                 and all(os.path.getmtime(op) >= os.path.getmtime(d) for d in deps)):
             continue

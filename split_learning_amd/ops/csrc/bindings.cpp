@@ -15,13 +15,12 @@ at::Tensor conv2d_wino_fused(const at::Tensor&, const at::Tensor&,
                              c10::optional<at::Tensor>, int, bool);
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor&, const at::Tensor&, int);
 // conv2d.hip
-at::Tensor pad_nchw(const at::Tensor&, int);
 at::Tensor conv2d_fwd(const at::Tensor&, const at::Tensor&, c10::optional<at::Tensor>,
-                      int, int, bool);
+                      int, int);
 at::Tensor conv2d_bwd_data(const at::Tensor&, const at::Tensor&, int, int, int, int);
-at::Tensor conv2d_bwd_weight(const at::Tensor&, const at::Tensor&, int, int, int, int,
-                             bool);
+at::Tensor conv2d_bwd_weight(const at::Tensor&, const at::Tensor&, int, int, int, int);
 at::Tensor conv2d_bwd_bias(const at::Tensor&);
+std::string conv_route(const std::string&, int, int, int, int, int, int, int, int);
 // norm.hip
 std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor&,
                                          c10::optional<at::Tensor>,
@@ -109,15 +108,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("flip") = false);
   m.def("conv2d_wino_bwdw_fused", &slk::conv2d_wino_bwdw_fused, py::arg("gy"),
         py::arg("x"), py::arg("pad") = 1);
-  m.def("pad_nchw", &slk::pad_nchw);
   m.def("conv2d_fwd", &slk::conv2d_fwd, py::arg("x"), py::arg("w"),
-        py::arg("bias"), py::arg("stride"), py::arg("pad"),
-        py::arg("x_is_padded") = false);
+        py::arg("bias"), py::arg("stride"), py::arg("pad"));
   m.def("conv2d_bwd_data", &slk::conv2d_bwd_data);
   m.def("conv2d_bwd_weight", &slk::conv2d_bwd_weight, py::arg("gy"), py::arg("x"),
-        py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("pad"),
-        py::arg("x_is_padded") = false);
+        py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("pad"));
   m.def("conv2d_bwd_bias", &slk::conv2d_bwd_bias);
+  m.def("conv_route", &slk::conv_route, py::arg("op"), py::arg("B"),
+        py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"), py::arg("K"),
+        py::arg("stride"), py::arg("pad"));
   m.def("bn2d_stats_fused", &slk::bn2d_stats_fused);
   m.def("bn2d_fwd", &slk::bn2d_fwd);
   m.def("bn2d_bwd", &slk::bn2d_bwd, py::arg("x"), py::arg("gy"),

@@ -6,12 +6,11 @@
 //
 // Round-2 findings (profiles/, conv_microbench + PMC on MI355X):
 // * the round-1 hypothesis "gathers are issue-bound" was WRONG at kernel
-//   grain: a bounds-free pre-padded gather (SLK_CONV_PAD=1 path below) ties
-//   the bounds-checked direct gather within noise (42.2 vs 42.7 us on
-//   conv1_2) because the core is barrier/latency-paced, not VALU-bound —
-//   while its pad/flipT prep kernels cost ~0.27 ms/step.  The DIRECT gather
-//   is therefore the default; the padded path stays selectable for A/B as
-//   the core gets faster.
+//   grain: a bounds-free pre-padded gather tied the bounds-checked direct
+//   gather within noise (42.2 vs 42.7 us on conv1_2) because the core is
+//   barrier/latency-paced, not VALU-bound — while its pad/flipT prep kernels
+//   cost ~0.27 ms/step.  The direct gather is the only one; the pre-padded
+//   experiment has been removed (profiles/SUMMARY.md keeps the numbers).
 // * the real levers are in tile_gemm.h (LDS ping-pong, batched reads) and
 //   split-K slab stores (AtomicStore at split 64 = 4M atomicAdds on a 65 KB
 //   output: the 512ch/2x2 tail layers ran 2x slower than MIOpen).
@@ -23,30 +22,15 @@
 // Geometry (KH, KW, stride, pad) is a TEMPLATE specialisation for the model
 // zoo's cases; runtime dims divide through FastDiv magics (common.h);
 // gathers are BRANCHLESS (clamped addresses + cndmask selects).
-#include <torch/extension.h>
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
+// Which kernel a call runs (direct here, or a Winograd form in wino.hip) is
+// decided by the routing table in conv_route.h.
+#include <tuple>
 
+#include "conv_route.h"
 #include "tile_gemm.h"
+#include "torch_util.h"
 
 namespace slk {
-
-// empty + single fill-KERNEL launch instead of at::zeros (no aten dispatch;
-// and never hipMemsetAsync — see slk_zero_async in common.h).
-static inline at::Tensor zeroed(at::IntArrayRef sizes, const at::TensorOptions& opt) {
-  auto t = at::empty(sizes, opt);
-  slk_zero_async(t.data_ptr<float>(), t.numel(),
-                 c10::hip::getCurrentHIPStream().stream());
-  return t;
-}
-
-static inline bool conv_pad_mode() {
-  static int v = [] {
-    const char* e = std::getenv("SLK_CONV_PAD");
-    return e ? atoi(e) : 0;
-  }();
-  return v != 0;
-}
 
 // wino.hip
 at::Tensor conv2d_wino(const at::Tensor&, const at::Tensor&,
@@ -56,66 +40,14 @@ at::Tensor conv2d_wino_fused(const at::Tensor&, const at::Tensor&,
                              c10::optional<at::Tensor>, int, bool);
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor&, const at::Tensor&, int);
 
-// fused-Winograd eligibility: shape constraints + grid fill.  The fused
-// kernel's base grid is (T/32) x (Cout/32); for FORWARD the measured
-// win/lose line falls at >= 256 base blocks (1 per CU) — below it the
-// ci-split can fill the grid but the forward still measured WORSE fused
-// (8x8 tails: 52.4 vs 49.9 us), so forward keeps the 256 rule.
-// BACKWARD-DATA additionally wins on the ci-split small-T tails and gets
-// its own extension at the conv2d_bwd_data call site (profiles/SUMMARY.md).
-static inline bool wino_fused_ok(int Cin, int Cout, int T, int OH, int OW) {
-  static int v = [] {
+// SLK_WINO level for conv_route.h, read once per process
+static int wino_level() {
+  static const int v = [] {
     const char* e = std::getenv("SLK_WINO");
     return e ? atoi(e) : 1;
   }();
-  if (v == 0) return false;
-  if ((OH | OW) & 1) return false;
-  if (Cout % 32 != 0 || T % 32 != 0 || Cin % 8 != 0) return false;
-  if (v >= 3) return true;  // force: ci-split fills the grid (sweeps)
-  return (long)(T / 32) * (Cout / 32) >= 256;
+  return v;
 }
-
-// Winograd routing (SLK_WINO=0 disables): F(2x2,3x3) beats the direct
-// implicit-GEMM kernel on the MEASURED win set only — square channel counts
-// at either end of the stack (64ch/32x32 and >=256ch tails); the 128ch
-// middle loses to V/M HBM inflation (tools/wino_check.py table in
-// profiles/SUMMARY.md).
-static inline bool wino_env_on() {
-  static int v = [] {
-    const char* e = std::getenv("SLK_WINO");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0;
-}
-
-static inline bool wino_wins_bwdw(int Ci, int Co, int H, int OH, int OW) {
-  static int v = [] {
-    const char* e = std::getenv("SLK_WINO");
-    return e ? atoi(e) : 1;
-  }();
-  if (v == 0) return false;
-  if ((OH | OW) & 1) return false;
-  if (v >= 2) return true;
-  // measured win set (tools/wino_check.py under SLK_WINO=0): square channel
-  // counts win everywhere EXCEPT the 4x4 layers, where T = B*4 makes the
-  // frequency GEMMs too small (512ch 4x4: 62 vs 48 us direct); the stem
-  // (3ch 32x32) also wins mildly (44.9 vs 49.3 us) — its direct form is a
-  // 9-n-tile tall-K pathology
-  return (Ci == Co && H != 4) || (Ci <= 4 && H >= 32);
-}
-
-static inline bool wino_wins(int Ci, int Co, int H, int KH, int KW, int stride,
-                             int OH, int OW) {
-  static int v = [] {
-    const char* e = std::getenv("SLK_WINO");
-    return e ? atoi(e) : 1;
-  }();
-  if (v == 0 || KH != 3 || KW != 3 || stride != 1) return false;
-  if ((OH | OW) & 1) return false;
-  if (v >= 2) return true;  // force (sweeps)
-  return Ci == Co && (Ci >= 256 || H >= 32);
-}
-
 
 struct ConvGeom {
   int B, Ci, H, W, Co, KH, KW, OH, OW, stride, pad;
@@ -147,7 +79,7 @@ struct Geo {
 
 __device__ __forceinline__ float sel0(float v, bool keep) { return keep ? v : 0.f; }
 
-// ---------------- forward: direct gather (default) ------------------------
+// ---------------- forward ---------------------------------------------------
 template <int CKH, int CKW, int CS>
 struct ConvFwdGather {
   using G = Geo<CKH, CKW, CS>;
@@ -189,42 +121,6 @@ struct ConvFwdGather {
     const int iwc = in ? iw : 0;
     const float v = x[c.boff + (ci * geo.H + ihc) * geo.W + iwc];
     return sel0(v, c.valid & kv & in);
-  }
-};
-
-// ---------------- forward: pre-padded bounds-free gather (SLK_CONV_PAD) ---
-template <int CKH, int CKW, int CS>
-struct ConvFwdGatherP {
-  using G = Geo<CKH, CKW, CS>;
-  const float* w;  // [Co, Ci, KH, KW] (or [Ci, Co, KHKW] flipT for bwd-data)
-  const float* x;  // [B, Ci, Hp, Wp] pre-padded: every tap address in-bounds
-  ConvGeom geo;    // H/W are the PADDED dims; geo.pad == 0
-
-  struct KCtx {};
-  __device__ KCtx prepK(int) const { return {}; }
-
-  struct ACtx { const float* row; bool valid; };
-  struct BCtx { const float* px; };
-
-  __device__ ACtx prepA(int, int m, bool valid, int) const {
-    return {w + (long)m * (geo.Ci * G::kh_kw(geo)), valid};
-  }
-  __device__ float loadA(const ACtx& c, const KCtx&, int k, bool kv) const {
-    return sel0(c.row[k], c.valid & kv);
-  }
-  __device__ BCtx prepB(int, int n, bool, int) const {
-    const unsigned b = geo.d_ohow.div(n);
-    const unsigned rem = geo.d_ohow.mod(n, b);
-    const unsigned oh = geo.d_ow.div(rem);
-    const unsigned ow = geo.d_ow.mod(rem, oh);
-    return {x + (long)b * geo.Ci * geo.H * geo.W
-              + (long)(oh * G::stride(geo)) * geo.W + ow * G::stride(geo)};
-  }
-  __device__ float loadB(const BCtx& c, const KCtx&, int k, bool kv) const {
-    int ci, kh, kw;
-    G::dk(geo, k, ci, kh, kw);   // SALU (k wave-uniform)
-    const int off = (ci * geo.H + kh) * geo.W + kw;
-    return sel0(c.px[off], kv);
   }
 };
 
@@ -330,13 +226,12 @@ struct ConvBwdDataStore {
 };
 
 // ---------------- backward weight ------------------------------------------
-// Direct gather; the gy A-side uses the prepK window hoist (fast flag).
-// PADDED=true additionally drops the x bounds math (SLK_CONV_PAD path).
-template <int CKH, int CKW, int CS, bool PADDED>
+// The gy A-side uses the prepK window hoist (fast flag).
+template <int CKH, int CKW, int CS>
 struct ConvBwdWeightGather {
   using G = Geo<CKH, CKW, CS>;
   const float* gy;  // [B, Co, OH, OW]
-  const float* x;   // [B, Ci, H, W] (padded dims when PADDED)
+  const float* x;   // [B, Ci, H, W]
   ConvGeom geo;
   bool fast;        // OH*OW % 16 == 0: window-hoisted A addressing
 
@@ -375,11 +270,6 @@ struct ConvBwdWeightGather {
     const unsigned rem = geo.d_ohow.mod(k, b);
     const unsigned oh = geo.d_ow.div(rem);
     const unsigned ow = geo.d_ow.mod(rem, oh);
-    if (PADDED) {
-      const long sc = (long)b * geo.Ci * geo.H * geo.W
-                    + (long)(oh * G::stride(geo)) * geo.W + ow * G::stride(geo);
-      return sel0(x[c.ciHW + c.kh * geo.W + c.kw + sc], kv);
-    }
     const int ih = (int)oh * G::stride(geo) - geo.pad + c.kh;
     const int iw = (int)ow * G::stride(geo) - geo.pad + c.kw;
     const bool in = (unsigned)ih < (unsigned)geo.H && (unsigned)iw < (unsigned)geo.W;
@@ -421,13 +311,12 @@ __global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
   }
 }
 
-static void slab_reduce(const at::Tensor& slab, int splits, at::Tensor& out,
-                        hipStream_t stream) {
-  const long numel = out.numel();
+// shared with wino.hip's ci-/tile-split slabs (declared in torch_util.h)
+void slab_reduce(const float* slab, int splits, float* out, long numel,
+                 hipStream_t stream) {
   const int grid = (int)std::min<long>((numel + 255) / 256, 4096);
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid), dim3(256), 0, stream,
-                     slab.data_ptr<float>(), splits, out.data_ptr<float>(),
-                     numel);
+                     slab, splits, out, numel);
 }
 
 // slab mode threshold: slab stores beat atomics once MANY splits pile on
@@ -449,83 +338,19 @@ static inline int slab_min_splits() {
 // (tens of MB) cost more in reduce than their atomics would
 static constexpr long SLK_SLAB_MAX_BYTES = 32l << 20;
 
-// ---------------- padding / weight-flip prep kernels -----------------------
-
-// x [BC, H, W] -> out [BC, H+2p, W+2p] zero-filled border, one coalesced
-// pass: one blockIdx.y per (b, c) plane, blockIdx.x strides the padded plane
-__global__ void pad_nchw_kernel(const float* __restrict__ x,
-                                float* __restrict__ out, int H, int W, int p,
-                                FastDiv d_wp) {
-  const int Hp = H + 2 * p, Wp = W + 2 * p;
-  const int plane = Hp * Wp;
-  const float* __restrict__ xin = x + (long)blockIdx.y * H * W;
-  float* __restrict__ po = out + (long)blockIdx.y * plane;
-  const int stride = gridDim.x * blockDim.x;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += stride) {
-    const int hp = d_wp.div((unsigned)i);
-    const int wp = d_wp.mod((unsigned)i, (unsigned)hp);
-    const int ih = hp - p, iw = wp - p;
-    const bool in = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-    po[i] = in ? xin[ih * W + iw] : 0.f;
-  }
-}
-
-// w [Co, Ci, KHKW] -> wt [Ci, Co, KHKW] with the tap index reversed
-// (kh, kw) -> (KH-1-kh, KW-1-kw) == r -> KHKW-1-r; output-coalesced
-__global__ void flipT_w_kernel(const float* __restrict__ w,
-                               float* __restrict__ wt, int Co, int Ci, int KK) {
-  const long total = (long)Co * Ci * KK;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    const int r = (int)(i % KK);
-    const long t = i / KK;
-    const int co = (int)(t % Co);
-    const long ci = t / Co;
-    wt[i] = w[((long)co * Ci + ci) * KK + (KK - 1 - r)];
-  }
-}
-
-at::Tensor pad_nchw(const at::Tensor& x, int p) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat);
-  if (p == 0) return x.contiguous();
-  auto xc = x.contiguous();
-  const long BC = (long)x.size(0) * x.size(1);
-  TORCH_CHECK(BC < 65536, "pad_nchw: B*C grid limit");
-  const int H = x.size(2), W = x.size(3);
-  auto out = at::empty({x.size(0), x.size(1), H + 2 * p, W + 2 * p}, x.options());
-  FastDiv d_wp;
-  d_wp.init(W + 2 * p);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int plane = (H + 2 * p) * (W + 2 * p);
-  const int gx = std::min(ceil_div(plane, 256), 16);
-  hipLaunchKernelGGL(pad_nchw_kernel, dim3(gx, (uint32_t)BC), dim3(256), 0,
-                     stream, xc.data_ptr<float>(), out.data_ptr<float>(), H, W,
-                     p, d_wp);
-  return out;
-}
-
-static at::Tensor flipT_w(const at::Tensor& w) {
-  auto wc = w.contiguous();
-  const int Co = w.size(0), Ci = w.size(1), KK = w.size(2) * w.size(3);
-  auto wt = at::empty({Ci, Co, w.size(2), w.size(3)}, w.options());
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const long total = (long)Co * Ci * KK;
-  const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(flipT_w_kernel, dim3(grid), dim3(256), 0, stream,
-                     wc.data_ptr<float>(), wt.data_ptr<float>(), Co, Ci, KK);
-  return wt;
-}
-
 // ---------------- host wrappers ----------------
 
-static ConvGeom make_geom(int B, int Ci, int H, int W, int Co, int KH, int KW,
-                          int stride, int pad) {
+static ConvShape conv_shape(int B, int Ci, int H, int W, int Co, int KH, int KW,
+                            int stride, int pad) {
+  return {B, Ci, H, W, Co, KH, KW, stride, pad};
+}
+
+static ConvGeom make_geom(const ConvShape& s) {
   ConvGeom g;
-  g.B = B; g.Ci = Ci; g.H = H; g.W = W; g.Co = Co; g.KH = KH; g.KW = KW;
-  g.stride = stride; g.pad = pad;
-  g.OH = (H + 2 * pad - KH) / stride + 1;
-  g.OW = (W + 2 * pad - KW) / stride + 1;
+  g.B = s.B; g.Ci = s.Ci; g.H = s.H; g.W = s.W; g.Co = s.Co; g.KH = s.KH;
+  g.KW = s.KW; g.stride = s.stride; g.pad = s.pad;
+  g.OH = s.OH();
+  g.OW = s.OW();
   g.d_ohow.init(g.OH * g.OW);
   g.d_ow.init(g.OW);
   g.d_hw.init(g.H * g.W);
@@ -552,22 +377,11 @@ static void dispatch_geom(const ConvGeom& g, F&& f) {
   }
 }
 
+// the gather specialisation for dispatch_geom's case index
 template <template <int, int, int> class Gather, int CASE>
-struct PickGather;
-template <template <int, int, int> class Gather>
-struct PickGather<Gather, 0> { using type = Gather<3, 3, 1>; };
-template <template <int, int, int> class Gather>
-struct PickGather<Gather, 1> { using type = Gather<3, 3, 2>; };
-template <template <int, int, int> class Gather>
-struct PickGather<Gather, 2> { using type = Gather<1, 1, 1>; };
-template <template <int, int, int> class Gather>
-struct PickGather<Gather, 3> { using type = Gather<4, 4, 4>; };
-template <template <int, int, int> class Gather>
-struct PickGather<Gather, 4> { using type = Gather<0, 0, 0>; };
-
-// bwd-weight needs the extra PADDED axis
-template <int A, int B, int C> using BwdWD = ConvBwdWeightGather<A, B, C, false>;
-template <int A, int B, int C> using BwdWP = ConvBwdWeightGather<A, B, C, true>;
+using PickGather = std::tuple_element_t<
+    CASE, std::tuple<Gather<3, 3, 1>, Gather<3, 3, 2>, Gather<1, 1, 1>,
+                     Gather<4, 4, 4>, Gather<0, 0, 0>>>;
 
 // split-K output plan: direct store (split 1), atomic accumulate (few
 // splits), or per-split slab + reduce (many splits)
@@ -601,188 +415,130 @@ static SplitPlan plan_split(int split_k, at::IntArrayRef out_sizes,
   return p;
 }
 
-// x_is_padded: caller already ran pad_nchw (only meaningful under
-// SLK_CONV_PAD=1, where functional.py saves x_pad from the forward)
+// The direct implicit-GEMM launch, shared by the three directions: pick the
+// split, plan the output (store / atomics / slabs), launch the geometry's
+// Gather{a, b, geo, extra...} and reduce the slabs.  make_store(buf,
+// accumulate, slab_stride) returns the direction's store functor; its type is
+// the kernel's Store parameter.  At split 1 a single block owns each output
+// tile, so every direction (bwd-weight included) stores directly.
+template <template <int, int, int> class Gather, typename MakeStore,
+          typename... Extra>
+static at::Tensor direct_gemm(const ConvGeom& geo, int M, int N, int K,
+                              at::IntArrayRef out_sizes,
+                              const at::TensorOptions& opt, const float* a,
+                              const float* b, MakeStore make_store,
+                              Extra... extra) {
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const int split_k = slk_effective_split(K, slk_pick_split_k(M, N, K, 1));
+  auto plan = plan_split(split_k, out_sizes, opt);
+  const auto st = make_store(plan.buf.data_ptr<float>(),
+                             !plan.slab && split_k > 1,
+                             plan.slab ? plan.out.numel() : 0);
+  dispatch_geom(geo, [&](auto ic) {
+    PickGather<Gather, decltype(ic)::value> g{a, b, geo, extra...};
+    slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
+  });
+  if (plan.slab) {
+    slab_reduce(plan.buf.data_ptr<float>(), split_k,
+                plan.out.data_ptr<float>(), plan.out.numel(), stream);
+  }
+  return plan.out;
+}
+
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
-                      c10::optional<at::Tensor> bias, int stride, int pad,
-                      bool x_is_padded) {
+                      c10::optional<at::Tensor> bias, int stride, int pad) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat);
   TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(1) == x.size(1));
-  if (!x_is_padded && !conv_pad_mode() && stride == 1 && w.size(2) == 3
-      && w.size(3) == 3) {
-    const int OHw = x.size(2) + 2 * pad - 2, OWw = x.size(3) + 2 * pad - 2;
-    const int Tw = x.size(0) * (OHw / 2) * (OWw / 2);
-    if (wino_fused_ok(x.size(1), w.size(0), Tw, OHw, OWw)) {
+  const ConvShape s = conv_shape(x.size(0), x.size(1), x.size(2), x.size(3),
+                                 w.size(0), w.size(2), w.size(3), stride, pad);
+  switch (route_fwd(s, wino_level())) {
+    case ConvRoute::WinoFused:
       return conv2d_wino_fused(x, w, bias, pad, /*flip=*/false);
-    }
-    if (wino_wins(x.size(1), w.size(0), x.size(2), 3, 3, 1, OHw, OWw)) {
+    case ConvRoute::Wino:
       return conv2d_wino(x, w, bias, pad, /*flip=*/false);
-    }
+    default:
+      break;
   }
-  const bool padded = x_is_padded || conv_pad_mode();
-  auto stream = c10::hip::getCurrentHIPStream().stream();
+  auto xc = x.contiguous();
   auto wc = w.contiguous();
-
-  at::Tensor xp = padded ? (x_is_padded ? x.contiguous() : pad_nchw(x, pad))
-                         : x.contiguous();
-  ConvGeom geo = padded
-      ? make_geom(xp.size(0), xp.size(1), xp.size(2), xp.size(3), w.size(0),
-                  w.size(2), w.size(3), stride, 0)
-      : make_geom(x.size(0), x.size(1), x.size(2), x.size(3), w.size(0),
-                  w.size(2), w.size(3), stride, pad);
-  const int M = geo.Co, N = geo.B * geo.OH * geo.OW, K = geo.Ci * geo.KH * geo.KW;
-  const int split_k = slk_effective_split(K, slk_pick_split_k(M, N, K, 1));
-  auto plan = plan_split(split_k, {geo.B, geo.Co, geo.OH, geo.OW}, x.options());
-
-  ConvFwdStore st{plan.buf.data_ptr<float>(),
-                  bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                  geo.Co, geo.OH * geo.OW, geo.d_ohow,
-                  !plan.slab && split_k > 1,
-                  plan.slab ? plan.out.numel() : 0};
-  dispatch_geom(geo, [&](auto ic) {
-    if (padded) {
-      using GT = typename PickGather<ConvFwdGatherP, decltype(ic)::value>::type;
-      GT g{wc.data_ptr<float>(), xp.data_ptr<float>(), geo};
-      slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-    } else {
-      using GT = typename PickGather<ConvFwdGather, decltype(ic)::value>::type;
-      GT g{wc.data_ptr<float>(), xp.data_ptr<float>(), geo};
-      slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-    }
-  });
-  if (plan.slab) slab_reduce(plan.buf, split_k, plan.out, stream);
-  return plan.out;
+  const ConvGeom geo = make_geom(s);
+  const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
+  return direct_gemm<ConvFwdGather>(
+      geo, geo.Co, geo.B * geo.OH * geo.OW, geo.Ci * geo.KH * geo.KW,
+      {geo.B, geo.Co, geo.OH, geo.OW}, x.options(), wc.data_ptr<float>(),
+      xc.data_ptr<float>(), [&](float* y, bool accumulate, long slab_stride) {
+        return ConvFwdStore{y, bp, geo.Co, geo.OH * geo.OW, geo.d_ohow,
+                            accumulate, slab_stride};
+      });
 }
 
 at::Tensor conv2d_bwd_data(const at::Tensor& gy, const at::Tensor& w, int stride,
                            int pad, int H, int W) {
   TORCH_CHECK(gy.is_cuda() && gy.dim() == 4 && gy.scalar_type() == at::kFloat);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int KH = w.size(2), KW = w.size(3);
-  const int Ci = w.size(1), Co = w.size(0);
-  const int B = gy.size(0);
+  const ConvShape s = conv_shape(gy.size(0), w.size(1), H, W, w.size(0),
+                                 w.size(2), w.size(3), stride, pad);
+  TORCH_CHECK(s.OH() == gy.size(2) && s.OW() == gy.size(3),
+              "bwd-data geometry mismatch");
   // gx = winograd-conv of gy with rotated/transposed weights at pad' = 2-p
-  if (stride == 1 && KH == 3 && KW == 3 && pad <= 2) {
-    const int Tw = B * (H / 2) * (W / 2);
-    bool fused = H % 2 == 0 && W % 2 == 0 && wino_fused_ok(Co, Ci, Tw, H, W);
-    // backward-data ONLY: the ci-split fused kernel also wins on the
-    // small-T high-channel tails (measured, 40-iter A/B under SLK_WINO=3:
-    // 256ch 8x8 44.6 vs 49.3 us, 256->512 4x4 31.6 vs 38.1, 512ch 4x4 45.3
-    // vs 49.9; the 2x2 layers lose 62 vs 35 and stay out).  Forward at the
-    // same shapes measured WORSE fused and keeps the >=256-block rule.
-    if (!fused && H % 2 == 0 && W % 2 == 0 && H >= 4 && Ci >= 64
-        && Ci % 32 == 0 && Co % 8 == 0 && Tw % 32 == 0
-        && (long)(Tw / 32) * (Ci / 32) >= 32 && wino_env_on()) {
-      fused = true;  // Ci >= 64: measured down to 64ch gx (24.4 vs 37.0 us)
-    }
-    if (fused) {
+  switch (route_bwd_data(s, wino_level())) {
+    case ConvRoute::WinoFused:
       return conv2d_wino_fused(gy, w, c10::nullopt, 2 - pad, /*flip=*/true);
-    }
-    if (wino_wins(Co, Ci, gy.size(2), 3, 3, 1, H, W)) {
+    case ConvRoute::Wino:
       return conv2d_wino(gy, w, c10::nullopt, 2 - pad, /*flip=*/true);
-    }
+    default:
+      break;
   }
-
-  if (conv_pad_mode() && stride == 1 && KH == KW && pad <= KH - 1) {
-    // gx = valid-conv(pad(gy, K-1-p), flipT(w)): bounds-free forward gather.
-    // Derivation: y[oh] sums x[oh - p + kh] => gx[ih] = sum_kh gy[ih + p - kh]
-    // = sum_kh' gy_pad[ih + kh'] with kh' = KH-1-kh and pad q = KH-1-p.
-    auto wt = flipT_w(w);
-    const int q = KH - 1 - pad;
-    auto gyp = pad_nchw(gy, q);
-    ConvGeom geo = make_geom(B, Co, gyp.size(2), gyp.size(3), Ci, KH, KW, 1, 0);
-    TORCH_CHECK(geo.OH == H && geo.OW == W, "bwd-data geometry mismatch");
-    const int M = Ci, N = B * H * W, K = Co * KH * KW;
-    const int split_k = slk_effective_split(K, slk_pick_split_k(M, N, K, 1));
-    auto plan = plan_split(split_k, {B, Ci, H, W}, gy.options());
-    ConvFwdStore st{plan.buf.data_ptr<float>(), nullptr, Ci, H * W, geo.d_ohow,
-                    !plan.slab && split_k > 1, plan.slab ? plan.out.numel() : 0};
-    dispatch_geom(geo, [&](auto ic) {
-      using GT = typename PickGather<ConvFwdGatherP, decltype(ic)::value>::type;
-      GT g{wt.data_ptr<float>(), gyp.data_ptr<float>(), geo};
-      slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-    });
-    if (plan.slab) slab_reduce(plan.buf, split_k, plan.out, stream);
-    return plan.out;
-  }
-
   auto gyc = gy.contiguous();
   auto wc = w.contiguous();
-  ConvGeom geo = make_geom(B, Ci, H, W, Co, KH, KW, stride, pad);
-  TORCH_CHECK(geo.OH == gy.size(2) && geo.OW == gy.size(3),
-              "bwd-data geometry mismatch");
-  const int M = geo.Ci, N = geo.B * H * W, K = geo.Co * KH * KW;
-  const int split_k = slk_effective_split(K, slk_pick_split_k(M, N, K, 1));
-  auto plan = plan_split(split_k, {B, Ci, H, W}, gy.options());
-  ConvBwdDataStore st{plan.buf.data_ptr<float>(), geo.Ci, H * W, geo.d_hw,
-                      !plan.slab && split_k > 1,
-                      plan.slab ? plan.out.numel() : 0};
-  dispatch_geom(geo, [&](auto ic) {
-    using GT = typename PickGather<ConvBwdDataGather, decltype(ic)::value>::type;
-    GT g{wc.data_ptr<float>(), gyc.data_ptr<float>(), geo};
-    slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-  });
-  if (plan.slab) slab_reduce(plan.buf, split_k, plan.out, stream);
-  return plan.out;
+  const ConvGeom geo = make_geom(s);
+  return direct_gemm<ConvBwdDataGather>(
+      geo, geo.Ci, geo.B * H * W, geo.Co * geo.KH * geo.KW,
+      {geo.B, geo.Ci, H, W}, gy.options(), wc.data_ptr<float>(),
+      gyc.data_ptr<float>(), [&](float* gx, bool accumulate, long slab_stride) {
+        return ConvBwdDataStore{gx, geo.Ci, H * W, geo.d_hw, accumulate,
+                                slab_stride};
+      });
 }
 
 at::Tensor conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x, int KH,
-                             int KW, int stride, int pad, bool x_is_padded) {
+                             int KW, int stride, int pad) {
   TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.scalar_type() == at::kFloat);
-  // Winograd weight-gradient.  FUSED twin first (in-kernel transforms,
-  // tile-axis reduction with per-slice slabs): measured faster than every
-  // alternative on ALL eligible shapes — 512ch 2x2: 13.2 us vs 29.1 routed,
-  // 512ch 4x4: 36.2 vs 48.2, 64->128: 33.5 vs 45.9 (profiles/SUMMARY.md).
-  // The transform+frequency-GEMM pipeline (conv2d_wino_bwdw) remains for
-  // Ci/Co not multiples of 32.
-  if (!x_is_padded && !conv_pad_mode() && stride == 1 && KH == 3 && KW == 3
-      && pad <= 2 && gy.size(2) % 2 == 0 && gy.size(3) % 2 == 0) {
-    static int wv = [] {
-      const char* e = std::getenv("SLK_WINO");
-      return e ? atoi(e) : 1;
-    }();
-    if (wv != 0 && x.size(1) % 32 == 0 && gy.size(1) % 32 == 0) {
-      return conv2d_wino_bwdw_fused(gy, x, pad);
-    }
-    if (wino_wins_bwdw(x.size(1), gy.size(1), x.size(2), gy.size(2),
-                       gy.size(3))) {
-      return conv2d_wino_bwdw(gy, x, pad);
-    }
-  }
-  const bool padded = x_is_padded || conv_pad_mode();
-  auto gyc = gy.contiguous();
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-
-  at::Tensor xp = padded ? (x_is_padded ? x.contiguous() : pad_nchw(x, pad))
-                         : x.contiguous();
-  ConvGeom geo = padded
-      ? make_geom(xp.size(0), xp.size(1), xp.size(2), xp.size(3), gy.size(1),
-                  KH, KW, stride, 0)
-      : make_geom(x.size(0), x.size(1), x.size(2), x.size(3), gy.size(1),
-                  KH, KW, stride, pad);
-  TORCH_CHECK(geo.OH == gy.size(2) && geo.OW == gy.size(3),
+  const ConvShape s = conv_shape(x.size(0), x.size(1), x.size(2), x.size(3),
+                                 gy.size(1), KH, KW, stride, pad);
+  TORCH_CHECK(s.OH() == gy.size(2) && s.OW() == gy.size(3),
               "bwd-weight geometry mismatch");
-  const int M = geo.Co, N = geo.Ci * KH * KW, K = geo.B * geo.OH * geo.OW;
-  const int split_k = slk_effective_split(K, slk_pick_split_k(M, N, K, 1));
-  auto plan = plan_split(split_k, {geo.Co, geo.Ci, KH, KW}, gy.options());
-  // bwd-weight always accumulates over K even at split 1 unless slab? No:
-  // at split 1 a single block owns each output tile -> direct store is fine.
-  AtomicStore st{plan.buf.data_ptr<float>(), N, !plan.slab && split_k > 1,
-                 plan.slab ? plan.out.numel() : 0};
+  switch (route_bwd_weight(s, wino_level())) {
+    case ConvRoute::WinoBwdWFused:
+      return conv2d_wino_bwdw_fused(gy, x, pad);
+    case ConvRoute::WinoBwdW:
+      return conv2d_wino_bwdw(gy, x, pad);
+    default:
+      break;
+  }
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
+  const ConvGeom geo = make_geom(s);
+  const int N = geo.Ci * KH * KW;
   const bool fast = (geo.OH * geo.OW) % SLK_BK == 0;
-  dispatch_geom(geo, [&](auto ic) {
-    if (padded) {
-      using GT = typename PickGather<BwdWP, decltype(ic)::value>::type;
-      GT g{gyc.data_ptr<float>(), xp.data_ptr<float>(), geo, fast};
-      slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-    } else {
-      using GT = typename PickGather<BwdWD, decltype(ic)::value>::type;
-      GT g{gyc.data_ptr<float>(), xp.data_ptr<float>(), geo, fast};
-      slk_launch_gemm(g, st, M, N, K, 1, split_k, stream);
-    }
-  });
-  if (plan.slab) slab_reduce(plan.buf, split_k, plan.out, stream);
-  return plan.out;
+  return direct_gemm<ConvBwdWeightGather>(
+      geo, geo.Co, N, geo.B * geo.OH * geo.OW, {geo.Co, geo.Ci, KH, KW},
+      gy.options(), gyc.data_ptr<float>(), xc.data_ptr<float>(),
+      [&](float* gw, bool accumulate, long slab_stride) {
+        return AtomicStore{gw, N, accumulate, slab_stride};
+      },
+      fast);
+}
+
+// which kernel the wrappers above would run for a conv shape, at this
+// process's SLK_WINO level (launches nothing; tests pin the table with it)
+std::string conv_route(const std::string& op, int B, int Ci, int H, int W,
+                       int Co, int K, int stride, int pad) {
+  const ConvShape s = conv_shape(B, Ci, H, W, Co, K, K, stride, pad);
+  if (op == "fwd") return conv_route_name(route_fwd(s, wino_level()));
+  if (op == "bwd_data") return conv_route_name(route_bwd_data(s, wino_level()));
+  TORCH_CHECK(op == "bwd_weight", "conv_route: op must be fwd, bwd_data or "
+              "bwd_weight, got ", op);
+  return conv_route_name(route_bwd_weight(s, wino_level()));
 }
 
 // per-channel sum of gy over (B, OH, OW) -> conv bias gradient
@@ -820,16 +576,14 @@ at::Tensor conv2d_bwd_bias(const at::Tensor& gy) {
   auto gyc = gy.contiguous();
   const int B = gy.size(0), C = gy.size(1), HW = gy.size(2) * gy.size(3);
   auto gb = at::empty({C}, gy.options());
-  long chunks = ((long)B * HW) / 4096;
-  if (chunks < 1) chunks = 1;
-  if (chunks > 16) chunks = 16;
+  const int chunks = reduce_chunks((long)B * HW);
   auto slab = at::empty({chunks, C}, gy.options());
   auto stream = c10::hip::getCurrentHIPStream().stream();
   hipLaunchKernelGGL(conv_bias_grad_kernel, dim3(C, (uint32_t)chunks), dim3(256),
                      0, stream, gyc.data_ptr<float>(), slab.data_ptr<float>(), B, C,
                      HW);
   hipLaunchKernelGGL(conv_bias_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256),
-                     0, stream, slab.data_ptr<float>(), (int)chunks,
+                     0, stream, slab.data_ptr<float>(), chunks,
                      gb.data_ptr<float>(), C);
   return gb;
 }

@@ -2,23 +2,10 @@
 // Serves Linear fwd/bwd (reference nn.Linear sites: src/model/VGG16_CIFAR10.py:107-117),
 // attention QK^T / PV batched matmuls (src/model/BERT_AGNEWS.py:66-74), and
 // LoRA adapters.  Transposes are handled by stride swaps — no data movement.
-#include <torch/extension.h>
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
-
 #include "tile_gemm.h"
+#include "torch_util.h"
 
 namespace slk {
-
-// empty + single fill-KERNEL launch instead of at::zeros (no aten dispatch;
-// and never hipMemsetAsync — see slk_zero_async in common.h).
-static inline at::Tensor zeroed(at::IntArrayRef sizes, const at::TensorOptions& opt) {
-  auto t = at::empty(sizes, opt);
-  slk_zero_async(t.data_ptr<float>(), t.numel(),
-                 c10::hip::getCurrentHIPStream().stream());
-  return t;
-}
-
 
 struct StridedGather {
   const float* A;

@@ -3,23 +3,9 @@
 // for normalisation, unbiased for running stats — done host-side in
 // ops/functional.py) so state_dict running stats stay .pth-compatible
 // (SURVEY.md §7 hard-part 2).
-#include <torch/extension.h>
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
-
-#include "common.h"
+#include "torch_util.h"
 
 namespace slk {
-
-// empty + single fill-KERNEL launch instead of at::zeros (no aten dispatch;
-// and never hipMemsetAsync — see slk_zero_async in common.h).
-static inline at::Tensor zeroed(at::IntArrayRef sizes, const at::TensorOptions& opt) {
-  auto t = at::empty(sizes, opt);
-  slk_zero_async(t.data_ptr<float>(), t.numel(),
-                 c10::hip::getCurrentHIPStream().stream());
-  return t;
-}
-
 
 // ---------------- BatchNorm2d ----------------
 
@@ -475,13 +461,6 @@ __global__ void bn_bwd_dx_kernel(const float* __restrict__ x,
   }
 }
 
-static inline int bn_chunks(long per_channel) {
-  long c = per_channel / 4096;
-  if (c < 1) c = 1;
-  if (c > 16) c = 16;
-  return (int)c;
-}
-
 template <typename T>
 static inline T* opt_ptr(const c10::optional<at::Tensor>& t) {
   return t.has_value() ? t->data_ptr<T>() : nullptr;
@@ -496,7 +475,7 @@ std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
   auto mean = at::empty({C}, x.options());
   auto invstd = at::empty({C}, x.options());
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int chunks = bn_chunks((long)B * HW);
+  const int chunks = reduce_chunks((long)B * HW);
   FastDiv d_hw;
   d_hw.init(HW);
   if (chunks == 1) {
@@ -567,7 +546,7 @@ std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor& x, const at::Tensor& ga
     y = at::empty({B, C, H / 2, W / 2}, x.options());
     idx = at::empty({B, C, H / 2, W / 2}, x.options().dtype(at::kByte));
   }
-  if (bn_chunks((long)B * HW) == 1) {
+  if (reduce_chunks((long)B * HW) == 1) {
     auto mean = at::empty({C}, x.options());
     auto invstd = at::empty({C}, x.options());
     if (!pool) y = at::empty_like(x);
@@ -636,7 +615,7 @@ static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tens
   auto sum_gy_xhat = at::empty({C}, x.options());
   auto gx = at::empty_like(x);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int rchunks = bn_chunks((long)B * HW);
+  const int rchunks = reduce_chunks((long)B * HW);
   const float inv_n = 1.0f / (float)((long)B * HW);
   FastDiv d_hw;
   d_hw.init(HW);

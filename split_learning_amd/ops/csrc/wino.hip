@@ -11,7 +11,7 @@
 // wins where the GEMM is compute-dominated — the high-Ci tail of VGG16 —
 // and loses to the direct implicit-GEMM kernel on the big-spatial low-Ci
 // layers where the 4x data inflation of V/M eats the MAC savings
-// (measured routing in conv2d.hip; MIOpen's advantage on those layers is a
+// (measured routing in conv_route.h; MIOpen's advantage on those layers is a
 // FUSED Winograd with in-kernel transforms).
 //
 // Backward-data reuses the whole machinery: gx = winograd-conv of gy with
@@ -20,12 +20,8 @@
 // V_x[f]^T, gw = G^T dU G) in both a transform+GEMM pipeline and a fully
 // FUSED kernel (wino_bwdw_fused_kernel).  The fully fused forward
 // (wino_fused_kernel) keeps the transforms in-kernel; routing between the
-// three forms is measured per shape (conv2d.hip).
-#include <torch/extension.h>
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
-
-#include "common.h"
+// three forms is measured per shape (conv_route.h).
+#include "torch_util.h"
 
 namespace slk {
 
@@ -317,7 +313,7 @@ constexpr int WF_VLD = WF_T + 1;    // V_lds[f][ci][t]
 // ci_per: the ci-range length per grid.z slice.  The output transform is
 // LINEAR in M, so slices transform their PARTIAL sums, each into its own
 // slab of y (y + blockIdx.z * B*Co*OH*OW), reduced in fixed order by
-// wino_slab_reduce_kernel — this fills the chip for small-T/high-Ci shapes
+// slab_reduce — this fills the chip for small-T/high-Ci shapes
 // whose natural grid is far below one block per CU, and unlike atomicAdd
 // gives the same sum every run.  Slice 0 adds the bias.
 template <bool FLIP>
@@ -684,18 +680,6 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
   }
 }
 
-__global__ void wino_slab_reduce_kernel(const float* __restrict__ slab,
-                                        int splits, float* __restrict__ out,
-                                        long numel) {
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < numel;
-       i += stride) {
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += slab[(long)k * numel + i];
-    out[i] = s;
-  }
-}
-
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
                                   int pad) {
   TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
@@ -731,21 +715,17 @@ at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
                      gyc.data_ptr<float>(), xc.data_ptr<float>(),
                      slab.data_ptr<float>(), B, Ci, H, W, Co, OH, OW, tH, tW,
                      pad, t_per, d_thw, d_tw);
-  auto gw = at::empty({Co, Ci, 3, 3}, x.options());
   if (splits == 1) {
     return slab.view({Co, Ci, 3, 3});
   }
-  const long numel = (long)Co * Ci * 9;
-  const int rgrid = (int)std::min<long>((numel + 255) / 256, 4096);
-  hipLaunchKernelGGL(wino_slab_reduce_kernel, dim3(rgrid), dim3(256), 0,
-                     stream, slab.data_ptr<float>(), splits,
-                     gw.data_ptr<float>(), numel);
+  auto gw = at::empty({Co, Ci, 3, 3}, x.options());
+  slab_reduce(slab.data_ptr<float>(), splits, gw.data_ptr<float>(), gw.numel(),
+              stream);
   return gw;
 }
 
 // fully-fused variant: transforms in-kernel, no V/M round trip.  Shape
-// requirements: Co % 32 == 0, T % 32 == 0, Ci % 8 == 0.  SLK_WINO_FUSED=0
-// falls back to the unfused pipeline (A/B).
+// requirements: Co % 32 == 0, T % 32 == 0, Ci % 8 == 0.
 at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
                              c10::optional<at::Tensor> bias, int pad,
                              bool flip) {
@@ -803,11 +783,8 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
                        pad, ci_per, CW, d_thw, d_tw);
   }
   if (splits > 1) {
-    const long numel = y.numel();
-    const int rgrid = (int)std::min<long>((numel + 255) / 256, 4096);
-    hipLaunchKernelGGL(wino_slab_reduce_kernel, dim3(rgrid), dim3(256), 0,
-                       stream, slab.data_ptr<float>(), splits,
-                       y.data_ptr<float>(), numel);
+    slab_reduce(slab.data_ptr<float>(), splits, y.data_ptr<float>(), y.numel(),
+                stream);
   }
   return y;
 }

@@ -135,10 +135,10 @@ def linear(x, weight, bias=None):
 # ---------------------------------------------------------------------------
 
 class Conv2dFn(Function):
-    """Implicit-GEMM conv on the MFMA tile framework.  The default path
-    gathers directly from the unpadded tensors (the bounds math measured
-    free — conv2d.hip round-2 notes); SLK_CONV_PAD=1 switches the C++ side
-    to the pre-padded bounds-free gathers for A/B experiments."""
+    """Implicit-GEMM conv on the MFMA tile framework, gathering directly
+    from the unpadded tensors (the bounds math measured free — conv2d.hip
+    round-2 notes).  3x3 stride-1 shapes may run a Winograd kernel instead:
+    native().conv_route(op, ...) names the kernel a shape takes."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, bias_grad_zero):

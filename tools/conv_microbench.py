@@ -86,8 +86,8 @@ def main():
         yt = torch.nn.functional.conv2d(xt, wt, None, s, 1)
         gy = torch.randn_like(yt)
 
-        # end-to-end per-call cost (any pad/flip prep of the SLK_CONV_PAD=1
-        # path is charged to the op, as in the training step)
+        # end-to-end per-call cost (transform, zero-fill and slab-reduce
+        # launches are charged to the op, as in the training step)
         ops = {
             "fwd": (lambda: n.conv2d_fwd(x, w, None, s, 1),
                     lambda: torch.nn.functional.conv2d(x, w, None, s, 1)),
