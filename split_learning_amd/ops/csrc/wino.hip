@@ -301,14 +301,64 @@ at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
 // pipeline's 4x data inflation).  A block owns a (32 co x 32 tile) output
 // patch across ALL 16 frequencies, so each 4x4 input patch is read once and
 // feeds every frequency.  Per wave: 16x16 (co, t) fragment x 16 freq = 16
-// f32x4 accumulators (64 AGPR).  K-loop over ci in steps of 8.
-// Weights arrive PRE-TRANSFORMED (U[16][Co][Ci], wino_wt_kernel — tiny).
+// f32x4 accumulators (64 registers).  K-loop over ci in steps of 8.
+// Weights arrive raw; U = G w G^T is computed while staging.
 constexpr int WF_CO = 32;   // block co tile
 constexpr int WF_T = 32;    // block tile-column tile
 constexpr int WF_CK = 8;    // ci step
-// LDS row strides padded to dodge the worst bank conflicts
-constexpr int WF_ULD = WF_CO + 1;   // U_lds[f][ci][co]
-constexpr int WF_VLD = WF_T + 1;    // V_lds[f][ci][t]
+// LDS operand layout, both operands and all three fused kernels:
+// [row 32][k 8][f 16] floats — the 16 frequency values of one (row, k) element
+// are contiguous, so an MFMA lane fetches a frequency quad of its (row, k)
+// with one ds_read_b128 (16 wide reads per wave per K-step).  Strides in
+// floats: k 20, row 168.  ds_read_b128 is served in four 16-lane groups
+// ({0-3,12-15,20-27}, {4-11,16-19,28-31}, +32) over 16 sixteen-byte slots;
+// lane (r = lane>>4, c = lane&15) reads slot (42c + 5r + const) mod 16 =
+// (10c + 5r) mod 16: within a group the r-even lanes take the eight even
+// slots and the r-odd lanes the eight odd ones, each once — conflict-free.
+// Staging stores are ds_write_b128 (8-lane groups, eight slots): k-fast
+// threads (weights, both bwd-weight operands) hit slots 5k mod 8, all
+// distinct; the row-fast V staging hits 42*row mod 8 = 2*row mod 8, a 2-way
+// conflict on 4 of the 8 stores a thread makes per step.
+constexpr int WF_KS = 20;                  // k stride
+constexpr int WF_RS = 168;                 // row stride
+constexpr int WF_OP = 32 * WF_RS;          // floats per staged operand (21 KB)
+
+// The 32 MFMAs of one K-step for a wave, operands read from the layout above.
+// pa / pb point at the lane's (row, k = lane>>4) element of each operand; the
+// kk = 1 half sits 4 k-rows further.  Reads for frequency quad g+1 are issued
+// before the MFMAs of quad g, and inside a quad the four kk = 0 MFMAs go
+// before the four kk = 1 ones, so no MFMA waits on the one just issued.  Each
+// acc[f] still receives kk = 0 then kk = 1 of its own frequency.
+__device__ __forceinline__ void wino_kstep_mfma(const float* pa,
+                                                const float* pb,
+                                                f32x4 (&acc)[16]) {
+  const f32x4* a0 = reinterpret_cast<const f32x4*>(pa);
+  const f32x4* a1 = reinterpret_cast<const f32x4*>(pa + 4 * WF_KS);
+  const f32x4* b0 = reinterpret_cast<const f32x4*>(pb);
+  const f32x4* b1 = reinterpret_cast<const f32x4*>(pb + 4 * WF_KS);
+  f32x4 ra0 = a0[0], rb0 = b0[0], ra1 = a1[0], rb1 = b1[0];
+  #pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const f32x4 ca0 = ra0, cb0 = rb0, ca1 = ra1, cb1 = rb1;
+    if (g < 3) {
+      ra0 = a0[g + 1];
+      rb0 = b0[g + 1];
+      ra1 = a1[g + 1];
+      rb1 = b1[g + 1];
+    }
+    // keep the reads above ahead of this quad's MFMAs: the scheduler
+    // otherwise sinks them to just before their first use
+    __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[g * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+          ca0[j], cb0[j], acc[g * 4 + j], 0, 0, 0);
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[g * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+          ca1[j], cb1[j], acc[g * 4 + j], 0, 0, 0);
+  }
+}
 
 // ci_per: the ci-range length per grid.z slice.  The output transform is
 // LINEAR in M, so slices transform their PARTIAL sums, each into its own
@@ -324,11 +374,11 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     int ci_per, int CW, FastDiv d_thw, FastDiv d_tw) {
   const int ci_begin = blockIdx.z * ci_per;
   const int ci_end = min(Ci, ci_begin + ci_per);
-  // single-buffer two-barrier loop: double buffering would cost 67.6 KB of
-  // LDS (2 blocks/CU); at 33.8 KB four blocks fit and the long 32-MFMA
-  // phase gives co-resident waves the latency cover instead
-  __shared__ float Ul[16 * WF_CK * WF_ULD];
-  __shared__ float Vl[16 * WF_CK * WF_VLD];
+  // single-buffer two-barrier loop: double buffering would cost 84 KB of
+  // LDS (1 block/CU); at 42 KB three blocks fit, which is what the
+  // launch bound allows anyway
+  __shared__ __attribute__((aligned(16))) float Ul[WF_OP];   // [co][ci][f]
+  __shared__ __attribute__((aligned(16))) float Vl[WF_OP];   // [t][ci][f]
 
   const int T = B * tH * tW;
   const int co0 = blockIdx.y * WF_CO;
@@ -369,8 +419,12 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
   // software pipeline: next step's 4x4 patch + 9 weight taps load into
   // registers UNDER the (long, 32-MFMA) compute phase; the transforms + LDS
   // stores run at the top of the next iteration
+  // the 9 taps stay in the registers their (4+4+1)-dword loads fill: as nine
+  // scalars the loop-carried copies out of those loads sat right behind them,
+  // with the vmcnt wait that exposes the whole global latency every step
   float d[4][4];
-  float wr[9];
+  f32x4 wq0, wq1;
+  float w8;
 
   auto load_regs = [&](int ci0) {
     const float* xp = x + xplane + (long)ci0 * H * W;
@@ -388,8 +442,10 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     const long wbase = FLIP
         ? ((long)(ci0 + w_ci) * CW + (co0 + w_co)) * 9
         : ((long)(co0 + w_co) * CW + (ci0 + w_ci)) * 9;
-    #pragma unroll
-    for (int k = 0; k < 9; ++k) wr[k] = w[wbase + (FLIP ? 8 - k : k)];
+    using f32x4u = __attribute__((ext_vector_type(4), aligned(4))) float;
+    wq0 = *reinterpret_cast<const f32x4u*>(w + wbase);
+    wq1 = *reinterpret_cast<const f32x4u*>(w + wbase + 4);
+    w8 = w[wbase + 8];
   };
 
   auto store_stage = [&]() {
@@ -401,15 +457,19 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
       u[2][bb] = d[2][bb] - d[1][bb];
       u[3][bb] = d[1][bb] - d[3][bb];
     }
+    f32x4* vp = reinterpret_cast<f32x4*>(&Vl[v_t * WF_RS + v_ci * WF_KS]);
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      Vl[((a * 4 + 0) * WF_CK + v_ci) * WF_VLD + v_t] = u[a][0] - u[a][2];
-      Vl[((a * 4 + 1) * WF_CK + v_ci) * WF_VLD + v_t] = u[a][1] + u[a][2];
-      Vl[((a * 4 + 2) * WF_CK + v_ci) * WF_VLD + v_t] = u[a][2] - u[a][1];
-      Vl[((a * 4 + 3) * WF_CK + v_ci) * WF_VLD + v_t] = u[a][1] - u[a][3];
+      vp[a] = f32x4{u[a][0] - u[a][2], u[a][1] + u[a][2],
+                    u[a][2] - u[a][1], u[a][1] - u[a][3]};
     }
     // U = G w G^T for this thread's (co, ci) pair — same op order as
     // wino_wt_kernel, so the result is bit-identical to the staged path
+    const float raw[9] = {wq0[0], wq0[1], wq0[2], wq0[3], wq1[0],
+                          wq1[1], wq1[2], wq1[3], w8};
+    float wr[9];
+    #pragma unroll
+    for (int k = 0; k < 9; ++k) wr[k] = raw[FLIP ? 8 - k : k];
     float t0[3], t1[3], t2[3], t3[3];
     #pragma unroll
     for (int bb = 0; bb < 3; ++bb) {
@@ -420,31 +480,24 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
       t3[bb] = g2;
     }
     const float* tr[4] = {t0, t1, t2, t3};
+    f32x4* up = reinterpret_cast<f32x4*>(&Ul[w_co * WF_RS + w_ci * WF_KS]);
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const float* t = tr[a];
-      Ul[((a * 4 + 0) * WF_CK + w_ci) * WF_ULD + w_co] = t[0];
-      Ul[((a * 4 + 1) * WF_CK + w_ci) * WF_ULD + w_co] = 0.5f * (t[0] + t[1] + t[2]);
-      Ul[((a * 4 + 2) * WF_CK + w_ci) * WF_ULD + w_co] = 0.5f * (t[0] - t[1] + t[2]);
-      Ul[((a * 4 + 3) * WF_CK + w_ci) * WF_ULD + w_co] = t[2];
+      up[a] = f32x4{t[0], 0.5f * (t[0] + t[1] + t[2]),
+                    0.5f * (t[0] - t[1] + t[2]), t[2]};
     }
   };
+
+  const float* pa = &Ul[(wco + frag_c) * WF_RS + frag_r * WF_KS];
+  const float* pb = &Vl[(wt + frag_c) * WF_RS + frag_r * WF_KS];
 
   load_regs(ci_begin);
   for (int ci0 = ci_begin; ci0 < ci_end; ci0 += WF_CK) {
     store_stage();
     __syncthreads();
     if (ci0 + WF_CK < ci_end) load_regs(ci0 + WF_CK);
-    #pragma unroll
-    for (int f = 0; f < 16; ++f) {
-      #pragma unroll
-      for (int kk = 0; kk < WF_CK / 4; ++kk) {
-        const int kr = kk * 4 + frag_r;
-        const float a = Ul[(f * WF_CK + kr) * WF_ULD + wco + frag_c];
-        const float b = Vl[(f * WF_CK + kr) * WF_VLD + wt + frag_c];
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[f], 0, 0, 0);
-      }
-    }
+    wino_kstep_mfma(pa, pb, acc);
     __syncthreads();
   }
 
@@ -539,8 +592,8 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
     const float* __restrict__ gy, const float* __restrict__ x,
     float* __restrict__ slab, int B, int Ci, int H, int W, int Co, int OH,
     int OW, int tH, int tW, int pad, int t_per, FastDiv d_thw, FastDiv d_tw) {
-  __shared__ float Gl[16 * 8 * 33];   // [f][tloc][co]
-  __shared__ float Xl[16 * 8 * 33];   // [f][tloc][ci]
+  __shared__ __attribute__((aligned(16))) float Gl[WF_OP];   // [co][tloc][f]
+  __shared__ __attribute__((aligned(16))) float Xl[WF_OP];   // [ci][tloc][f]
 
   const int T = B * tH * tW;
   const int ci0 = blockIdx.y * 32;
@@ -607,14 +660,13 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
     const float r1c0 = gg[0][0] + gg[1][0], r1c1 = gg[0][1] + gg[1][1];
     const float r2c0 = gg[0][0] - gg[1][0], r2c1 = gg[0][1] - gg[1][1];
     const float r3c0 = -gg[1][0], r3c1 = -gg[1][1];
+    f32x4* gp4 = reinterpret_cast<f32x4*>(&Gl[s_ch * WF_RS + s_t * WF_KS]);
+    f32x4* xp4 = reinterpret_cast<f32x4*>(&Xl[s_ch * WF_RS + s_t * WF_KS]);
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const float c0 = a == 0 ? r0c0 : a == 1 ? r1c0 : a == 2 ? r2c0 : r3c0;
       const float c1 = a == 0 ? r0c1 : a == 1 ? r1c1 : a == 2 ? r2c1 : r3c1;
-      Gl[((a * 4 + 0) * 8 + s_t) * 33 + s_ch] = c0;
-      Gl[((a * 4 + 1) * 8 + s_t) * 33 + s_ch] = c0 + c1;
-      Gl[((a * 4 + 2) * 8 + s_t) * 33 + s_ch] = c0 - c1;
-      Gl[((a * 4 + 3) * 8 + s_t) * 33 + s_ch] = -c1;
+      gp4[a] = f32x4{c0, c0 + c1, c0 - c1, -c1};
     }
     // B^T d B
     float u[4][4];
@@ -627,28 +679,20 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
     }
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      Xl[((a * 4 + 0) * 8 + s_t) * 33 + s_ch] = u[a][0] - u[a][2];
-      Xl[((a * 4 + 1) * 8 + s_t) * 33 + s_ch] = u[a][1] + u[a][2];
-      Xl[((a * 4 + 2) * 8 + s_t) * 33 + s_ch] = u[a][2] - u[a][1];
-      Xl[((a * 4 + 3) * 8 + s_t) * 33 + s_ch] = u[a][1] - u[a][3];
+      xp4[a] = f32x4{u[a][0] - u[a][2], u[a][1] + u[a][2],
+                     u[a][2] - u[a][1], u[a][1] - u[a][3]};
     }
   };
+
+  const float* pa = &Gl[(wco + frag_c) * WF_RS + frag_r * WF_KS];
+  const float* pb = &Xl[(wci + frag_c) * WF_RS + frag_r * WF_KS];
 
   load_regs(t_begin);
   for (int t0 = t_begin; t0 < t_end; t0 += 8) {
     store_stage();
     __syncthreads();
     if (t0 + 8 < t_end) load_regs(t0 + 8);
-    #pragma unroll
-    for (int f = 0; f < 16; ++f) {
-      #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int kr = kk * 4 + frag_r;
-        const float a = Gl[(f * 8 + kr) * 33 + wco + frag_c];
-        const float b = Xl[(f * 8 + kr) * 33 + wci + frag_c];
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[f], 0, 0, 0);
-      }
-    }
+    wino_kstep_mfma(pa, pb, acc);
     __syncthreads();
   }
 
