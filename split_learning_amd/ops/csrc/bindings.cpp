@@ -10,6 +10,7 @@ at::Tensor colsum_f32(const at::Tensor&);
 // wino.hip
 at::Tensor conv2d_wino(const at::Tensor&, const at::Tensor&,
                        c10::optional<at::Tensor>, int, bool);
+int conv2d_wino_slabs(int, int, int);
 at::Tensor conv2d_wino_bwdw(const at::Tensor&, const at::Tensor&, int);
 at::Tensor conv2d_wino_fused(const at::Tensor&, const at::Tensor&,
                              c10::optional<at::Tensor>, int, bool);
@@ -101,6 +102,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_wino", &slk::conv2d_wino, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("pad") = 1,
         py::arg("flip") = false);
+  m.def("conv2d_wino_slabs", &slk::conv2d_wino_slabs, py::arg("co"),
+        py::arg("ci"), py::arg("tiles"));
   m.def("conv2d_wino_bwdw", &slk::conv2d_wino_bwdw, py::arg("gy"),
         py::arg("x"), py::arg("pad") = 1);
   m.def("conv2d_wino_fused", &slk::conv2d_wino_fused, py::arg("x"),

@@ -71,10 +71,13 @@ __global__ void gemm_slab_reduce_kernel(const float* __restrict__ slab, int spli
   }
 }
 
-// split_k > 1: every split writes its own slab, reduced into c afterwards
+// split_k > 1: every split writes its own slab, reduced into c afterwards —
+// or, with keep_slabs, handed back unreduced as [splits * numel(c)] for a
+// consumer that sums them itself (c is then left untouched)
 static void launch_strided(const at::Tensor& a2, const at::Tensor& b2, at::Tensor& c,
                            bool ta, bool tb, const c10::optional<at::Tensor>& bias,
-                           bool accumulate, int split_k) {
+                           bool accumulate, int split_k,
+                           at::Tensor* keep_slabs = nullptr) {
   const bool batched = a2.dim() == 3;
   const int nb = batched ? a2.size(0) : 1;
   const int M = ta ? a2.size(-1) : a2.size(-2);
@@ -108,7 +111,9 @@ static void launch_strided(const at::Tensor& a2, const at::Tensor& b2, at::Tenso
   st.slab_stride = split_k > 1 ? numel : 0;
 
   slk_launch_gemm(g, st, M, N, K, nb, split_k, stream, slk_use_big(M, N));
-  if (split_k > 1) {
+  if (split_k > 1 && keep_slabs != nullptr) {
+    *keep_slabs = slab;
+  } else if (split_k > 1) {
     const int grid = (int)std::min<long>((numel + 255) / 256, 4096);
     hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3(grid), dim3(256), 0, stream,
                        slab.data_ptr<float>(), split_k, c.data_ptr<float>(), numel);
@@ -146,6 +151,37 @@ at::Tensor matmul_f32(const at::Tensor& a, const at::Tensor& b, bool ta, bool tb
   }
   launch_strided(a, b, c, ta, tb, c10::nullopt, accumulate, split_k);
   return c;
+}
+
+// slabs matmul_f32 splits a fresh [nb, M, K] @ [nb, K, N] into (1: no split)
+int matmul_f32_slab_count(int nb, int M, int N, int K) {
+  const bool big = slk_use_big(M, N);
+  return slk_effective_split(
+      K, slk_pick_split_k(M, N, K, nb, big ? SLK_BM2 : SLK_BM,
+                          big ? SLK_BN2 : SLK_BN));
+}
+
+// Batched a @ b (3-D, no transposes) with matmul_f32's split-K choice, the
+// slabs left unreduced: returns [splits, nb, M, N], of which the caller adds
+// slab 0, 1, ... in order as gemm_slab_reduce_kernel would.  The Winograd
+// output transform takes its M this way (wino.hip).
+at::Tensor matmul_f32_slabs(const at::Tensor& a, const at::Tensor& b) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 3 && b.dim() == 3 &&
+              a.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat,
+              "matmul_f32_slabs: 3-D fp32 GPU tensors");
+  TORCH_CHECK(a.numel() < (1ll << 31) && b.numel() < (1ll << 31),
+              "matmul_f32_slabs: int32 gather offsets (tensor too large)");
+  TORCH_CHECK(a.size(0) == b.size(0) && a.size(2) == b.size(1),
+              "matmul_f32_slabs: shape mismatch");
+  const int nb = a.size(0), M = a.size(1), K = a.size(2), N = b.size(2);
+  // the effective count: launch_strided maps it onto itself
+  const int split_k = matmul_f32_slab_count(nb, M, N, K);
+  at::Tensor c, slabs;
+  if (split_k == 1) c = at::empty({1, nb, M, N}, a.options());
+  else c = at::empty({0}, a.options());   // options carrier only
+  launch_strided(a, b, c, false, false, c10::nullopt, false, split_k, &slabs);
+  if (!slabs.defined()) return c;
+  return slabs.view({-1, nb, M, N});
 }
 
 at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w,

@@ -7,7 +7,8 @@
 // patch, overlap 2).  2.25x fewer MACs than direct: the elementwise product
 // becomes 16 frequency-batched GEMMs  M[f] = U[f][Co,Ci] @ V[f][Ci,T]
 // (T = B * OH/2 * OW/2) which run on the existing MFMA tile framework as ONE
-// batched launch.  Unfused (transforms round-trip V/M through HBM), so it
+// batched launch.  Unfused (transforms round-trip V/M through HBM; the GEMM's
+// split-K slabs are summed by the output transform), so it
 // wins where the GEMM is compute-dominated — the high-Ci tail of VGG16 —
 // and loses to the direct implicit-GEMM kernel on the big-spatial low-Ci
 // layers where the 4x data inflation of V/M eats the MAC savings
@@ -27,17 +28,20 @@ namespace slk {
 
 // weight transform U[f] = (G g G^T)[f] over the weight's true dims
 // (Cw0, Cw1) = (w.size(0), w.size(1)); FLIP writes U[f][Cw1][Cw0] with the
-// taps rotated 180 degrees (the bwd-data weight), else U[f][Cw0][Cw1]
+// taps rotated 180 degrees (the bwd-data weight), else U[f][Cw0][Cw1].
+// (block, nblocks): the launch's blocks that work on this transform — the
+// whole grid of wino_wt_kernel, a share of wino_wt_in_kernel's
 template <bool FLIP>
-__global__ void wino_wt_kernel(const float* __restrict__ w,
-                               float* __restrict__ U, int Cw0, int Cw1) {
+__device__ __forceinline__ void wino_wt_body(const float* __restrict__ w,
+                                             float* __restrict__ U, int Cw0,
+                                             int Cw1, int block, int nblocks) {
   // thread per (channel pair, frequency ROW): 4x the threads of the obvious
   // per-pair mapping — the small conv weights (64x64: 4096 pairs) gave a
   // 16-BLOCK grid on a 256-CU chip and the launch ran latency-bound at 7-9
   // us; the 4x re-read of w is noise next to that
   const long total = (long)Cw0 * Cw1;
-  const long tstride = (long)gridDim.x * blockDim.x;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < 4 * total;
+  const long tstride = (long)nblocks * blockDim.x;
+  for (long e = (long)block * blockDim.x + threadIdx.x; e < 4 * total;
        e += tstride) {
     const int a = (int)(e & 3);          // frequency row
     const long i = e >> 2;
@@ -70,14 +74,14 @@ __global__ void wino_wt_kernel(const float* __restrict__ w,
 
 // input transform V[f][Ci][T], T = B*tH*tW, tile t = (b, th, tw); the 4x4
 // patch starts at (th*2 - pad, tw*2 - pad), zero-padded at the borders
-__global__ void wino_in_kernel(const float* __restrict__ x,
-                               float* __restrict__ V, int B, int Ci, int H,
-                               int W, int tH, int tW, int pad, FastDiv d_T,
-                               FastDiv d_thw, FastDiv d_tw) {
+__device__ __forceinline__ void wino_in_body(
+    const float* __restrict__ x, float* __restrict__ V, int B, int Ci, int H,
+    int W, int tH, int tW, int pad, const FastDiv& d_T, const FastDiv& d_thw,
+    const FastDiv& d_tw, int block, int nblocks) {
   const int T = B * tH * tW;
   const long total = (long)Ci * T;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+  const long stride = (long)nblocks * blockDim.x;
+  for (long i = (long)block * blockDim.x + threadIdx.x; i < total;
        i += stride) {
     const unsigned cc = d_T.div((unsigned)i);
     const unsigned t = d_T.mod((unsigned)i, cc);
@@ -123,40 +127,106 @@ __global__ void wino_in_kernel(const float* __restrict__ x,
   }
 }
 
-// output transform y[b][co][2th..][2tw..] = A^T M A (+bias)
-__global__ void wino_out_kernel(const float* __restrict__ Mm,
-                                float* __restrict__ y,
-                                const float* __restrict__ bias, int B, int Co,
-                                int OH, int OW, int tH, int tW, FastDiv d_T,
-                                FastDiv d_thw, FastDiv d_tw) {
+__global__ void wino_in_kernel(const float* __restrict__ x,
+                               float* __restrict__ V, int B, int Ci, int H,
+                               int W, int tH, int tW, int pad, FastDiv d_T,
+                               FastDiv d_thw, FastDiv d_tw) {
+  wino_in_body(x, V, B, Ci, H, W, tH, tW, pad, d_T, d_thw, d_tw, blockIdx.x,
+               gridDim.x);
+}
+
+template <bool FLIP>
+__global__ void wino_wt_kernel(const float* __restrict__ w,
+                               float* __restrict__ U, int Cw0, int Cw1) {
+  wino_wt_body<FLIP>(w, U, Cw0, Cw1, blockIdx.x, gridDim.x);
+}
+
+// Both operand transforms of conv2d_wino in ONE launch: they are independent
+// (U from w, V from x) and each alone underfills or barely fills the chip for
+// a few microseconds, so as two launches the second waits out the first's
+// drain.  The first in_blocks blocks run the input transform — the short
+// one, so its blocks retire while the weight transform's stream in behind
+// them — the rest the weight transform; each element is computed by the same
+// code as in the separate kernels.
+template <bool FLIP>
+__global__ void wino_wt_in_kernel(const float* __restrict__ w,
+                                  float* __restrict__ U, int Cw0, int Cw1,
+                                  const float* __restrict__ x,
+                                  float* __restrict__ V, int B, int Ci, int H,
+                                  int W, int tH, int tW, int pad, FastDiv d_T,
+                                  FastDiv d_thw, FastDiv d_tw, int in_blocks) {
+  if ((int)blockIdx.x < in_blocks) {
+    wino_in_body(x, V, B, Ci, H, W, tH, tW, pad, d_T, d_thw, d_tw, blockIdx.x,
+                 in_blocks);
+  } else {
+    wino_wt_body<FLIP>(w, U, Cw0, Cw1, blockIdx.x - in_blocks,
+                       gridDim.x - in_blocks);
+  }
+}
+
+// output transform y[b][co][2th..][2tw..] = A^T M A (+bias), with the
+// frequency GEMM's split-K sum folded in: M arrives as `splits` slabs
+// (slab_stride floats apart) and each element is summed here in
+// gemm_slab_reduce_kernel's order and form (0.f, then slab 0, 1, ...), so the
+// separate reduce launch and the write and re-read of the summed M go away and
+// the result keeps its bits.
+//
+// A block owns 64 consecutive (co, t) pairs; wave a sums frequency row a
+// (f = 4a .. 4a+3) of each, so a pair's 16*splits loads spread over four
+// threads — the 2x2 layers have only Co*T = 16 K pairs, a quarter of a block
+// per CU at a thread per pair.  The sums meet in LDS and thread (pair, a) then
+// forms output pixel (a >> 1, a & 1) with the expression order of a
+// thread-per-pair transform.
+__global__ __launch_bounds__(256) void wino_out_kernel(
+    const float* __restrict__ Mm, int splits, long slab_stride,
+    float* __restrict__ y, const float* __restrict__ bias, int B, int Co,
+    int OH, int OW, int tH, int tW, FastDiv d_T, FastDiv d_thw, FastDiv d_tw) {
+  __shared__ float ml[16][64];
   const int T = B * tH * tW;
   const long total = (long)Co * T;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    const unsigned co = d_T.div((unsigned)i);
-    const unsigned t = d_T.mod((unsigned)i, co);
-    const unsigned b = d_thw.div(t);
-    const unsigned rem = d_thw.mod(t, b);
-    const unsigned th = d_tw.div(rem);
-    const unsigned tw = d_tw.mod(rem, th);
-    float m[4][4];
+  const int p = threadIdx.x & 63;
+  const int a = threadIdx.x >> 6;
+  for (long i0 = (long)blockIdx.x * 64; i0 < total; i0 += (long)gridDim.x * 64) {
+    const long i = i0 + p;
+    const bool live = i < total;
+    const unsigned co = d_T.div((unsigned)(live ? i : total - 1));
+    const unsigned t = d_T.mod((unsigned)(live ? i : total - 1), co);
+    const float* mp = Mm + ((long)(a * 4) * Co + co) * T + t;
+    const long fs = (long)Co * T;   // frequency stride
+    float m[4];
     #pragma unroll
-    for (int f = 0; f < 16; ++f)
-      m[f >> 2][f & 3] = Mm[((long)f * Co + co) * T + t];
-    // A^T m: [m0+m1+m2, m1-m2-m3]
-    float u[2][4];
-    #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      u[0][bb] = m[0][bb] + m[1][bb] + m[2][bb];
-      u[1][bb] = m[1][bb] - m[2][bb] - m[3][bb];
+    for (int bb = 0; bb < 4; ++bb) m[bb] = mp[bb * fs];
+    if (splits > 1) {
+      #pragma unroll
+      for (int bb = 0; bb < 4; ++bb) m[bb] = 0.f + m[bb];
+      for (int k = 1; k < splits; ++k) {
+        const float* mk = mp + (long)k * slab_stride;
+        #pragma unroll
+        for (int bb = 0; bb < 4; ++bb) m[bb] += mk[bb * fs];
+      }
     }
-    const float bv = bias != nullptr ? bias[co] : 0.f;
-    float* yp = y + ((long)b * Co + co) * OH * OW + (long)th * 2 * OW + tw * 2;
-    yp[0] = u[0][0] + u[0][1] + u[0][2] + bv;
-    yp[1] = u[0][1] - u[0][2] - u[0][3] + bv;
-    yp[OW] = u[1][0] + u[1][1] + u[1][2] + bv;
-    yp[OW + 1] = u[1][1] - u[1][2] - u[1][3] + bv;
+    #pragma unroll
+    for (int bb = 0; bb < 4; ++bb) ml[a * 4 + bb][p] = m[bb];
+    __syncthreads();
+    if (live) {
+      // row oi of A^T m: [m0+m1+m2, m1-m2-m3]; then the same across columns
+      const int oi = a >> 1, oj = a & 1;
+      float u[4];
+      #pragma unroll
+      for (int bb = 0; bb < 4; ++bb) {
+        u[bb] = oi == 0 ? ml[0 + bb][p] + ml[4 + bb][p] + ml[8 + bb][p]
+                        : ml[4 + bb][p] - ml[8 + bb][p] - ml[12 + bb][p];
+      }
+      const float bv = bias != nullptr ? bias[co] : 0.f;
+      const unsigned b = d_thw.div(t);
+      const unsigned rem = d_thw.mod(t, b);
+      const unsigned th = d_tw.div(rem);
+      const unsigned tw = d_tw.mod(rem, th);
+      float* yp = y + ((long)b * Co + co) * OH * OW + (long)(th * 2 + oi) * OW
+                  + tw * 2 + oj;
+      *yp = oj == 0 ? u[0] + u[1] + u[2] + bv : u[1] - u[2] - u[3] + bv;
+    }
+    __syncthreads();
   }
 }
 
@@ -228,11 +298,32 @@ __global__ void wino_gw_kernel(const float* __restrict__ dU,
   }
 }
 
-// host entry: 3x3 stride-1 conv via F(2x2,3x3); flip=true computes the
-// bwd-data conv (weights rotated + Co/Ci transposed, pad' = 2 - pad)
 at::Tensor matmul_f32(const at::Tensor&, const at::Tensor&, bool, bool,
                       c10::optional<at::Tensor>, bool);
+at::Tensor matmul_f32_slabs(const at::Tensor&, const at::Tensor&);
+int matmul_f32_slab_count(int, int, int, int);
 
+// split-K slabs wino_out_kernel sums for Co output and Ci input channels over
+// T tiles (M[f] = U[f][Co,Ci] @ V[f][Ci,T], batch 16)
+int conv2d_wino_slabs(int Co, int Ci, int T) {
+  return matmul_f32_slab_count(16, Co, T, Ci);
+}
+
+// SLK_WINO_PIPE (A/B and bisection only, read once), default 3: bit 0 = both
+// operand transforms in one launch (wino_wt_in_kernel), bit 1 = the output
+// transform sums the GEMM's split-K slabs.  0 is the five-launch form: wt, in,
+// GEMM, its slab reduce (as matmul_f32 does for every other caller), out.
+// Every value gives the same bits.
+static int wino_pipe_mode() {
+  static int v = [] {
+    const char* e = std::getenv("SLK_WINO_PIPE");
+    return e ? atoi(e) : 3;
+  }();
+  return v;
+}
+
+// host entry: 3x3 stride-1 conv via F(2x2,3x3); flip=true computes the
+// bwd-data conv (weights rotated + Co/Ci transposed, pad' = 2 - pad)
 at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
                        c10::optional<at::Tensor> bias, int pad, bool flip) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat);
@@ -248,46 +339,56 @@ at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
   const int tH = OH / 2, tW = OW / 2;
   const int T = B * tH * tW;
   auto stream = c10::hip::getCurrentHIPStream().stream();
+  FastDiv d_T, d_thw, d_tw;
+  d_T.init(T);
+  d_thw.init(tH * tW);
+  d_tw.init(tW);
 
+  const int mode = wino_pipe_mode();
   auto U = at::empty({16, Co, Ci}, x.options());
   auto V = at::empty({16, Ci, T}, x.options());
-  {
-    const long tot = (long)Co * Ci * 4;   // thread per (pair, freq row)
-    const int grid = (int)std::min<long>((tot + 255) / 256, 4096);
-    // always the WEIGHT's own dims; FLIP handles the transpose internally
+  // weight transform: thread per (pair, freq row), always over the WEIGHT's
+  // own dims (FLIP handles the transpose internally); input transform:
+  // thread per (ci, tile)
+  const int wt_grid =
+      (int)std::min<long>(((long)Co * Ci * 4 + 255) / 256, 4096);
+  const int in_grid = (int)std::min<long>(((long)Ci * T + 255) / 256, 8192);
+  const int Cw0 = (int)w.size(0), Cw1 = (int)w.size(1);
+  if (mode & 1) {
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(in_grid + wt_grid), dim3(256), 0,
+                         stream, wc.data_ptr<float>(), U.data_ptr<float>(),
+                         Cw0, Cw1, xc.data_ptr<float>(), V.data_ptr<float>(),
+                         B, Ci, H, W, tH, tW, pad, d_T, d_thw, d_tw, in_grid);
+    };
+    if (flip) launch(wino_wt_in_kernel<true>);
+    else launch(wino_wt_in_kernel<false>);
+  } else {
     if (flip) {
-      hipLaunchKernelGGL(wino_wt_kernel<true>, dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL(wino_wt_kernel<true>, dim3(wt_grid), dim3(256), 0,
                          stream, wc.data_ptr<float>(), U.data_ptr<float>(),
-                         (int)w.size(0), (int)w.size(1));
+                         Cw0, Cw1);
     } else {
-      hipLaunchKernelGGL(wino_wt_kernel<false>, dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL(wino_wt_kernel<false>, dim3(wt_grid), dim3(256), 0,
                          stream, wc.data_ptr<float>(), U.data_ptr<float>(),
-                         (int)w.size(0), (int)w.size(1));
+                         Cw0, Cw1);
     }
-  }
-  {
-    FastDiv d_T, d_thw, d_tw;
-    d_T.init(T);
-    d_thw.init(tH * tW);
-    d_tw.init(tW);
-    const long tot = (long)Ci * T;
-    const int grid = (int)std::min<long>((tot + 255) / 256, 8192);
-    hipLaunchKernelGGL(wino_in_kernel, dim3(grid), dim3(256), 0, stream,
+    hipLaunchKernelGGL(wino_in_kernel, dim3(in_grid), dim3(256), 0, stream,
                        xc.data_ptr<float>(), V.data_ptr<float>(), B, Ci, H, W,
                        tH, tW, pad, d_T, d_thw, d_tw);
   }
-  // M[f] = U[f] @ V[f]: one batched MFMA GEMM launch (batch = 16)
-  auto Mm = matmul_f32(U, V, false, false, c10::nullopt, false);
+  // M[f] = U[f] @ V[f]: one batched MFMA GEMM launch (batch = 16); its
+  // split-K slabs [splits, 16, Co, T] go to the output transform unreduced
+  auto Mm = (mode & 2)
+      ? matmul_f32_slabs(U, V)
+      : matmul_f32(U, V, false, false, c10::nullopt, false).unsqueeze(0);
   auto y = at::empty({B, Co, OH, OW}, x.options());
   {
-    FastDiv d_T, d_thw, d_tw;
-    d_T.init(T);
-    d_thw.init(tH * tW);
-    d_tw.init(tW);
-    const long tot = (long)Co * T;
-    const int grid = (int)std::min<long>((tot + 255) / 256, 8192);
+    const long blocks = ((long)Co * T + 63) / 64;   // 64 (co, t) pairs each
+    const int grid = (int)std::min<long>(blocks, 8192);
     hipLaunchKernelGGL(wino_out_kernel, dim3(grid), dim3(256), 0, stream,
-                       Mm.data_ptr<float>(), y.data_ptr<float>(),
+                       Mm.data_ptr<float>(), (int)Mm.size(0), 16l * Co * T,
+                       y.data_ptr<float>(),
                        bias.has_value() ? bias->data_ptr<float>() : nullptr,
                        B, Co, OH, OW, tH, tW, d_T, d_thw, d_tw);
   }
