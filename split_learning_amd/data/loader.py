@@ -50,5 +50,13 @@ def data_loader(data_name: str, batch_size: int,
     else:
         ds = TensorDataset(x, y)
     gen = torch.Generator().manual_seed(seed * 7919 + 13) if train else None
-    return DataLoader(ds, batch_size=batch_size, shuffle=train, drop_last=drop_last,
-                      num_workers=0, generator=gen)
+    loader = DataLoader(ds, batch_size=batch_size, shuffle=train,
+                        drop_last=drop_last, num_workers=0, generator=gen)
+    # real padded data (AGNEWS) names its pad id; synthetic ids are drawn from
+    # [1, vocab) and carry no padding
+    if real is not None:
+        from .real import pad_token_id
+        loader.pad_token_id = pad_token_id(data_name)
+    else:
+        loader.pad_token_id = None
+    return loader

@@ -92,6 +92,16 @@ def _load_agnews(train: bool):
             torch.tensor(labels, dtype=torch.int64))
 
 
+# Datasets whose real loader pads samples to a fixed length, and the id it
+# pads with (BertTokenizer's [PAD] is id 0).  Models derive their attention
+# mask from it (models/bert.py mask_pad_token_id).
+PAD_TOKEN_IDS = {"AGNEWS": 0}
+
+
+def pad_token_id(data_name: str) -> Optional[int]:
+    return PAD_TOKEN_IDS.get(data_name)
+
+
 _SC_CLASSES = ["yes", "no", "up", "down", "left", "right", "on", "off", "stop", "go"]
 
 

@@ -78,7 +78,15 @@ class BertSdpaSelfAttention(nn.Module):
         q = self.query(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         k = self.key(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         v = self.value(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
-        ctx = attention_core(q, k, v, dropout_p=self.dropout.p, training=self.training)
+        if attention_mask is None:
+            ctx = attention_core(q, k, v, dropout_p=self.dropout.p, training=self.training)
+        else:
+            # [B,S] mask, 1 = token, 0 = pad (any dtype): the reference adds
+            # (1 - mask) * -10000 to the scaled scores before the softmax
+            key_bias = (1.0 - attention_mask.to(torch.float32)) * -10000.0
+            ctx = attention_core(q, k, v, dropout_p=self.dropout.p,
+                                 training=self.training, key_bias=key_bias,
+                                 heads=H)
         return ctx.reshape(B, H, S, hd).permute(0, 2, 1, 3).reshape(B, S, E)
 
 
@@ -114,8 +122,9 @@ class BertAttention(nn.Module):
         self.self = BertSdpaSelfAttention(hidden_size, num_attention_heads, dropout_prob)
         self.output = BertSelfOutput(hidden_size, dropout_prob)
 
-    def forward(self, hidden_states):
-        return self.output(self.self(hidden_states), hidden_states)
+    def forward(self, hidden_states, attention_mask=None):
+        return self.output(self.self(hidden_states, attention_mask),
+                           hidden_states)
 
 
 class BertIntermediate(nn.Module):
@@ -147,8 +156,8 @@ class BertLayer(nn.Module):
         self.intermediate = BertIntermediate(hidden_size, intermediate_size)
         self.output = BertOutput(hidden_size, intermediate_size, dropout_prob)
 
-    def forward(self, hidden_states):
-        attn = self.attention(hidden_states)
+    def forward(self, hidden_states, attention_mask=None):
+        attn = self.attention(hidden_states, attention_mask)
         return self.output(self.intermediate(attn), attn)
 
 
@@ -172,8 +181,22 @@ class BertClassifier(nn.Module):
         return self.classifier(self.dropout(pooled))
 
 
+def _derive_pad_mask(model, ids, attention_mask):
+    """attention_mask for a partition that owns layer 1: the caller's, else
+    (ids != mask_pad_token_id) when that attribute is set.  Device ops only
+    (no host sync), so a captured step stays capturable."""
+    if attention_mask is None and model.mask_pad_token_id is not None:
+        return ids != model.mask_pad_token_id
+    return attention_mask
+
+
 class BERT_AGNEWS(PartitionedModel):
     TOTAL_UNITS = 15
+    # pad id to derive the attention mask from the token ids when no mask is
+    # passed (set by the runtime for datasets that pad).  Only a partition
+    # that owns layer 1 sees ids; later stages stay unmasked unless a caller
+    # passes a mask.
+    mask_pad_token_id = None
 
     def __init__(self, vocab_size=28996, hidden_size=768, num_attention_heads=12,
                  intermediate_size=3072, max_position_embeddings=512, type_vocab_size=2,
@@ -202,13 +225,15 @@ class BERT_AGNEWS(PartitionedModel):
         if self._active(15):
             self.layer15 = BertClassifier(Hd, 4)
 
-    def forward(self, input_ids=None, token_type_ids=None, **kwargs):
+    def forward(self, input_ids=None, token_type_ids=None, attention_mask=None,
+                **kwargs):
         x = input_ids
         if self._active(1):
+            attention_mask = _derive_pad_mask(self, x, attention_mask)
             x = self.layer1(x, token_type_ids)
         for i in range(2, 14):
             if self._active(i):
-                x = getattr(self, f"layer{i}")(x)
+                x = getattr(self, f"layer{i}")(x, attention_mask)
         if self._active(14):
             x = self.layer14(x)
         if self._active(15):
@@ -218,6 +243,7 @@ class BERT_AGNEWS(PartitionedModel):
 
 class BERT_EMOTION(PartitionedModel):
     TOTAL_UNITS = 27
+    mask_pad_token_id = None  # as BERT_AGNEWS
 
     def __init__(self, start_layer=0, end_layer=27, vocab_size=30522, hidden_size=768,
                  intermediate_size=3072, num_attention_heads=12, num_labels=4,
@@ -247,6 +273,7 @@ class BERT_EMOTION(PartitionedModel):
 
     def forward(self, x, attention_mask=None, token_type_ids=None):
         if self._active(1):
+            attention_mask = _derive_pad_mask(self, x, attention_mask)
             x = self.layer1(x, token_type_ids)
         for i in range(2, 26):
             if not self._active(i):

@@ -72,7 +72,14 @@ at::Tensor embedding_bwd(const at::Tensor&, const at::Tensor&, int64_t, int64_t)
 // attention.hip
 std::vector<at::Tensor> attn_fwd(const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, double, double, int64_t,
-                                 c10::optional<at::Tensor>);
+                                 c10::optional<at::Tensor>,
+                                 c10::optional<at::Tensor>, int64_t);
+std::vector<at::Tensor> attn_softmax_fwd(const at::Tensor&,
+                                         c10::optional<at::Tensor>, int64_t,
+                                         double, double, int64_t,
+                                         c10::optional<at::Tensor>);
+at::Tensor attn_softmax_bwd(const at::Tensor&, const at::Tensor&,
+                            c10::optional<at::Tensor>, double, double);
 // loss.hip
 at::Tensor softmax_fwd(const at::Tensor&);
 at::Tensor softmax_bwd(const at::Tensor&, const at::Tensor&);
@@ -155,7 +162,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &slk::embedding_bwd);
   m.def("attn_fwd", &slk::attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
+        py::arg("heads") = 1);
+  m.def("attn_softmax_fwd", &slk::attn_softmax_fwd, py::arg("scores"),
+        py::arg("key_bias"), py::arg("heads"), py::arg("scale"),
+        py::arg("p") = 0.0, py::arg("seed") = 0,
         py::arg("offset") = py::none());
+  m.def("attn_softmax_bwd", &slk::attn_softmax_bwd, py::arg("g_dropped"),
+        py::arg("probs"), py::arg("mask"), py::arg("scale"), py::arg("p") = 0.0);
   m.def("softmax_fwd", &slk::softmax_fwd);
   m.def("softmax_bwd", &slk::softmax_bwd);
   m.def("ce_fwd", &slk::ce_fwd);

@@ -484,8 +484,10 @@ class AttnFn(Function):
     and the kernel-produced mask (identical math to the unfused path)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, p, seed, offset_t):
-        out, probs, mask = native().attn_fwd(q, k, v, scale, p, seed, offset_t)
+    def forward(ctx, q, k, v, scale, p, seed, offset_t, key_bias=None,
+                heads=1):
+        out, probs, mask = native().attn_fwd(q, k, v, scale, p, seed, offset_t,
+                                             key_bias, heads)
         ctx.save_for_backward(q, k, v, probs, mask)
         ctx.scale = scale
         ctx.p = float(p)
@@ -516,7 +518,7 @@ class AttnFn(Function):
         gs = gs * ctx.scale
         gq = _matmul_raw(gs, k)
         gk = _matmul_raw(gs, q, trans_a=True)
-        return gq, gk, gv, None, None, None, None
+        return gq, gk, gv, None, None, None, None, None, None
 
 
 def attn_fused_ok(q) -> bool:
@@ -527,9 +529,19 @@ def attn_fused_ok(q) -> bool:
     return s <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
 
 
-def attention(q, k, v, scale, dropout_p=0.0, training=False):
+def _key_bias_arg(key_bias):
+    """additive [B, S] key bias as the kernels take it: fp32, contiguous, no
+    gradient (a padding mask is constant)."""
+    if key_bias is None:
+        return None
+    return key_bias.detach().to(torch.float32).contiguous()
+
+
+def attention(q, k, v, scale, dropout_p=0.0, training=False, key_bias=None,
+              heads=1):
     """Fused SDPA with optional in-kernel attention dropout;
-    inputs [BH, S, hd] contiguous."""
+    inputs [BH, S, hd] contiguous.  key_bias [BH/heads, S] is added to the
+    scaled scores of every head and query row of its sample."""
     p = float(dropout_p) if training else 0.0
     if p > 0.0:
         counter = _counter_for(q.device)
@@ -538,7 +550,45 @@ def attention(q, k, v, scale, dropout_p=0.0, training=False):
     else:
         seed, offset_t = 0, None
     return AttnFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), scale,
-                        p, seed, offset_t)
+                        p, seed, offset_t, _key_bias_arg(key_bias), int(heads))
+
+
+class AttnProbsFn(Function):
+    """dropout(softmax(scores * scale + key_bias)) in ONE kernel per direction
+    (attention.hip attn_softmax_fwd / attn_softmax_bwd): the masked GEMM
+    chain's only launch between its two GEMMs.  Saves the CLEAN probs and the
+    kernel-produced keep-mask; the bias is constant and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, scores, key_bias, heads, scale, p, seed, offset_t):
+        probs, dropped, mask = native().attn_softmax_fwd(
+            scores, key_bias, heads, scale, p, seed, offset_t)
+        ctx.save_for_backward(probs, mask)
+        ctx.scale = scale
+        ctx.p = float(p)
+        return dropped
+
+    @staticmethod
+    def backward(ctx, g):
+        probs, mask = ctx.saved_tensors
+        gs = native().attn_softmax_bwd(g.contiguous(), probs,
+                                       mask if ctx.p > 0.0 else None,
+                                       ctx.scale, ctx.p)
+        return gs, None, None, None, None, None, None
+
+
+def attn_probs(scores, key_bias, heads, scale, dropout_p=0.0, training=False):
+    """Attention probabilities from raw [BH, S, S] scores with an additive
+    [BH/heads, S] key bias (or None) and in-kernel dropout."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0:
+        counter = _counter_for(scores.device)
+        counter.add_(1)
+        seed, offset_t = _DROPOUT_STATE["seed"], counter
+    else:
+        seed, offset_t = 0, None
+    return AttnProbsFn.apply(scores.contiguous(), _key_bias_arg(key_bias),
+                             int(heads), float(scale), p, seed, offset_t)
 
 
 # ---------------------------------------------------------------------------

@@ -149,13 +149,22 @@ class HipMultiheadAttention(nn.MultiheadAttention):
     """
 
     def forward(self, query, key, value, **kwargs):  # type: ignore[override]
+        # The native path computes plain or key-padded self-attention and
+        # returns no weights.  What it cannot honour goes to the stock
+        # forward: an attn_mask, is_causal, or weights explicitly asked for
+        # (need_weights left at its default keeps the native path, as before).
         if (not _use_native("attn", query) or (query is not key)
-                or (key is not value) or not self.batch_first):
+                or (key is not value) or not self.batch_first
+                or query.dim() != 3
+                or kwargs.get("attn_mask") is not None
+                or kwargs.get("is_causal", False)
+                or kwargs.get("need_weights", False)):
             return super().forward(query, key, value, **kwargs)
         x = query  # [B, S, E]
         B, S, E = x.shape
         H = self.num_heads
         hd = E // H
+        key_bias = _key_padding_bias(kwargs.get("key_padding_mask"), B, S)
         qkv = hf.linear(x, self.in_proj_weight, self.in_proj_bias)  # [B,S,3E]
         q, k, v = qkv.split(E, dim=-1)
         scale = 1.0 / math.sqrt(hd)
@@ -167,7 +176,8 @@ class HipMultiheadAttention(nn.MultiheadAttention):
             v = v.reshape(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd)
             # fused SDPA kernel, in-kernel attention dropout (round 2)
             ctxv = hf.attention(q, k, v, scale, dropout_p=self.dropout,
-                                training=self.training)
+                                training=self.training, key_bias=key_bias,
+                                heads=H)
             ctxv = ctxv.reshape(B, H, S, hd).permute(0, 2, 1, 3).reshape(B, S, E)
         elif hf.use_lib_mm(B * H, S, S, hd):
             # library route (rocBLAS batched GEMM): keep [B,H,S,hd] strided
@@ -176,10 +186,18 @@ class HipMultiheadAttention(nn.MultiheadAttention):
             q = q.reshape(B, S, H, hd).transpose(1, 2)
             k = k.reshape(B, S, H, hd).transpose(1, 2)
             v = v.reshape(B, S, H, hd).transpose(1, 2)
-            scores = torch.matmul(q, k.transpose(-1, -2)) * scale
-            probs = hf.softmax_lastdim(scores)
-            if self.dropout > 0.0:
-                probs = hf.dropout(probs, self.dropout, self.training)
+            if key_bias is not None:
+                # masked: scale + bias + softmax + dropout in one launch on
+                # [BH,S,S] views of the library GEMM's scores
+                scores = torch.matmul(q, k.transpose(-1, -2))
+                probs = hf.attn_probs(scores.reshape(B * H, S, S), key_bias,
+                                      H, scale, self.dropout, self.training
+                                      ).reshape(B, H, S, S)
+            else:
+                scores = torch.matmul(q, k.transpose(-1, -2)) * scale
+                probs = hf.softmax_lastdim(scores)
+                if self.dropout > 0.0:
+                    probs = hf.dropout(probs, self.dropout, self.training)
             ctxv = torch.matmul(probs, v)  # [B, H, S, hd]
             ctxv = ctxv.transpose(1, 2).reshape(B, S, E)
         else:
@@ -187,14 +205,37 @@ class HipMultiheadAttention(nn.MultiheadAttention):
             q = q.reshape(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd)
             k = k.reshape(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd)
             v = v.reshape(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd)
-            scores = hf.matmul_f32(q, k, trans_b=True) * scale
-            probs = hf.softmax_lastdim(scores)
-            if self.dropout > 0.0:
-                probs = hf.dropout(probs, self.dropout, self.training)
+            if key_bias is not None:
+                probs = hf.attn_probs(hf.matmul_f32(q, k, trans_b=True),
+                                      key_bias, H, scale, self.dropout,
+                                      self.training)
+            else:
+                scores = hf.matmul_f32(q, k, trans_b=True) * scale
+                probs = hf.softmax_lastdim(scores)
+                if self.dropout > 0.0:
+                    probs = hf.dropout(probs, self.dropout, self.training)
             ctxv = hf.matmul_f32(probs, v)  # [B*H, S, hd]
             ctxv = ctxv.reshape(B, H, S, hd).permute(0, 2, 1, 3).reshape(B, S, E)
         out = hf.linear(ctxv, self.out_proj.weight, self.out_proj.bias)
         return out, None
+
+
+def _key_padding_bias(key_padding_mask, B, S):
+    """nn.MultiheadAttention's key_padding_mask as an additive [B, S] bias:
+    bool (True = ignore this key) becomes -inf, a float mask is already
+    additive.  Device ops only."""
+    if key_padding_mask is None:
+        return None
+    if tuple(key_padding_mask.shape) != (B, S):
+        raise ValueError(f"key_padding_mask must be [{B}, {S}], got "
+                         f"{tuple(key_padding_mask.shape)}")
+    if key_padding_mask.dtype == torch.bool:
+        return torch.zeros(B, S, dtype=torch.float32,
+                           device=key_padding_mask.device).masked_fill_(
+                               key_padding_mask, float("-inf"))
+    if not key_padding_mask.is_floating_point():
+        raise TypeError("key_padding_mask must be bool or floating point")
+    return key_padding_mask.to(torch.float32)
 
 
 _FATTN_FORCE = os.environ.get("SLK_FATTN", "0") == "1"
@@ -213,10 +254,18 @@ def _fused_attn_worth_it(bh, s_len, dropout_p, training) -> bool:
 
 
 def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
-                   scale: Optional[float] = None):
-    """scaled-dot-product attention on [B*H, S, hd] tensors via HIP kernels."""
+                   scale: Optional[float] = None, key_bias=None,
+                   heads: int = 1):
+    """scaled-dot-product attention on [B*H, S, hd] tensors via HIP kernels.
+
+    key_bias ([B, S] additive float, B = q.shape[0] // heads) is added to the
+    scaled scores of every head and query row of its sample before the
+    softmax: a padding mask.  Without it every route is the unmasked one."""
     hd = q.shape[-1]
     s = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if key_bias is not None:
+        return _attention_core_biased(q, k, v, dropout_p, training, s,
+                                      key_bias, heads)
     if (_use_native("attn", q) and "fattn" not in _DBG_TORCH and q.dim() == 3
             and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
             and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
@@ -230,6 +279,35 @@ def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
             probs = hf.dropout(probs, dropout_p, training)
         return hf.matmul_f32(probs, v)
     scores = torch.matmul(q, k.transpose(-1, -2)) * s
+    probs = F.softmax(scores, dim=-1)
+    if dropout_p > 0.0:
+        probs = F.dropout(probs, dropout_p, training)
+    return torch.matmul(probs, v)
+
+
+def _attention_core_biased(q, k, v, dropout_p, training, s, key_bias, heads):
+    """attention_core with an additive key bias; same three routes."""
+    hd = q.shape[-1]
+    if q.dim() != 3 or q.shape[0] % heads != 0 or \
+            tuple(key_bias.shape) != (q.shape[0] // heads, q.shape[1]):
+        raise ValueError(
+            f"key_bias must be [B*H / heads, S] for q {tuple(q.shape)} and "
+            f"heads={heads}, got {tuple(key_bias.shape)}")
+    if (_use_native("attn", q) and "fattn" not in _DBG_TORCH
+            and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
+            and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
+                                     training)):
+        return hf.attention(q, k, v, s, dropout_p=dropout_p, training=training,
+                            key_bias=key_bias, heads=heads)
+    if _use_native("attn", q):
+        # GEMM -> ONE scale+bias+softmax+dropout launch -> GEMM
+        scores = hf.matmul_f32(q, k, trans_b=True)
+        probs = hf.attn_probs(scores, key_bias, heads, s, dropout_p, training)
+        return hf.matmul_f32(probs, v)
+    BH, S, _ = q.shape
+    scores = torch.matmul(q, k.transpose(-1, -2)) * s
+    scores = (scores.view(BH // heads, heads, S, S)
+              + key_bias.to(scores.dtype)[:, None, None, :]).view(BH, S, S)
     probs = F.softmax(scores, dim=-1)
     if dropout_p > 0.0:
         probs = F.dropout(probs, dropout_p, training)

@@ -166,6 +166,11 @@ class ClientRuntime:
                                             self.learning["batch-size"],
                                             self.label_count, train=True,
                                             seed=self.client_id)
+        if self.model_name == "BERT" and self.model._active(1):
+            # the partition that sees token ids masks the loader's padding
+            # (None for synthetic data: no padding, unmasked attention)
+            self.model.mask_pad_token_id = getattr(self.train_loader,
+                                                   "pad_token_id", None)
 
         # per-round scheduler policy overrides travel in START (epochs,
         # sync-first, sda-size, time limit — the variant policies set these)

@@ -30,6 +30,9 @@ def get_val(model_name: str, data_name: str, state_dict_full, logger=None,
     model.to(device).eval()
 
     loader = data_loader(data_name, batch_size=64, distribution=None, train=False)
+    if model_name == "BERT":
+        # padded test data is masked, as the reference's validation does
+        model.mask_pad_token_id = getattr(loader, "pad_token_id", None)
     total = correct = 0
     loss_sum = 0.0
     with torch.no_grad():

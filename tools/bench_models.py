@@ -23,7 +23,7 @@ LEARNING = {"learning-rate": 5e-4, "weight-decay": 0.01, "momentum": 0.5}
 
 
 def bench_model(model, data, cut, batch, steps=64, warmup=16, lora=False,
-                graphs=False):
+                graphs=False, bert_pad_frac=None):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     s1 = build_partition(model, data, [0, cut]).to(dev).train()
@@ -41,6 +41,15 @@ def bench_model(model, data, cut, batch, steps=64, warmup=16, lora=False,
     else:
         x = torch.randn(batch, *shape, device=dev)
     y = torch.randint(0, n_labels, (batch,), device=dev)
+    if model == "BERT" and bert_pad_frac is not None:
+        # padded-batch arm: the tail of every sample is pad id 0 and both
+        # partitions are told the pad id (only the one that owns layer 1 sees
+        # ids and masks).  0.0 pads nothing but still runs the masked path.
+        n_pad = int(round(shape[0] * float(bert_pad_frac)))
+        if n_pad > 0:
+            x[:, shape[0] - n_pad:] = 0
+        s1.mask_pad_token_id = 0
+        s2.mask_pad_token_id = 0
 
     last = {}
 
@@ -87,6 +96,8 @@ def bench_model(model, data, cut, batch, steps=64, warmup=16, lora=False,
         "ms_per_step": round(dt / steps * 1e3, 3),
         "samples_per_sec": round(steps * batch / dt, 1),
         "lora": lora, "graphs": graphs,
+        **({"bert_pad_frac": bert_pad_frac}
+           if model == "BERT" and bert_pad_frac is not None else {}),
         "loss": round(float(last["loss"].detach()), 4),
     }
 
@@ -97,12 +108,23 @@ if __name__ == "__main__":
     # the capture grad steal removed the per-parameter accumulate-add kernels
     # from the captured step (~200 for BERT+LoRA); re-measured after it:
     # BERT 1145 vs 1060 eager, MobileNet 9851 vs 7868 eager.
-    # --eager disables all.
+    # --eager disables all.  --bert-pad-frac F (opt-in) pads the tail of each
+    # BERT sample and turns the attention padding mask on; --only MODEL runs
+    # one arm.
     eager = "--eager" in sys.argv
+    pad_frac = None
+    if "--bert-pad-frac" in sys.argv:
+        pad_frac = float(sys.argv[sys.argv.index("--bert-pad-frac") + 1])
+    only = None
+    if "--only" in sys.argv:
+        only = sys.argv[sys.argv.index("--only") + 1]
     for m, d, c, b, lora, g in [("VGG16", "CIFAR10", 7, 32, False, True),
                                 ("BERT", "AGNEWS", 2, 32, True, True),
                                 ("KWT", "SPEECHCOMMANDS", 7, 32, False, True),
                                 ("MobileNetv1", "CIFAR10", 40, 32, False, True),
                                 ("ViT", "CIFAR10", 6, 32, False, True)]:
-        r = bench_model(m, d, c, b, lora=lora, graphs=(g and not eager))
+        if only is not None and m != only:
+            continue
+        r = bench_model(m, d, c, b, lora=lora, graphs=(g and not eager),
+                        bert_pad_frac=pad_frac)
         print(json.dumps(r), flush=True)
