@@ -15,7 +15,13 @@ at::Tensor conv2d_wino_bwdw(const at::Tensor&, const at::Tensor&, int);
 at::Tensor conv2d_wino_fused(const at::Tensor&, const at::Tensor&,
                              c10::optional<at::Tensor>, int, bool);
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor&, const at::Tensor&, int);
+std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor&,
+                                                   const at::Tensor&,
+                                                   const at::Tensor&, int, int);
+std::tuple<int, int, int, int> conv2d_bwd_pair_splits(int, int, int, int, int, int);
 // conv2d.hip
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>> conv2d_bwd(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, int, int, bool, bool);
 at::Tensor conv2d_fwd(const at::Tensor&, const at::Tensor&, c10::optional<at::Tensor>,
                       int, int);
 at::Tensor conv2d_bwd_data(const at::Tensor&, const at::Tensor&, int, int, int, int);
@@ -123,6 +129,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_data", &slk::conv2d_bwd_data);
   m.def("conv2d_bwd_weight", &slk::conv2d_bwd_weight, py::arg("gy"), py::arg("x"),
         py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("pad"));
+  m.def("conv2d_bwd", &slk::conv2d_bwd, py::arg("gy"), py::arg("x"),
+        py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("need_gx"),
+        py::arg("need_gw"));
+  m.def("conv2d_bwd_pair", &slk::conv2d_bwd_pair, py::arg("gy"), py::arg("x"),
+        py::arg("w"), py::arg("pad") = 1, py::arg("interleave") = -1);
+  m.def("conv2d_bwd_pair_splits", &slk::conv2d_bwd_pair_splits, py::arg("B"),
+        py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"),
+        py::arg("pad") = 1);
   m.def("conv2d_bwd_bias", &slk::conv2d_bwd_bias);
   m.def("conv_route", &slk::conv_route, py::arg("op"), py::arg("B"),
         py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"), py::arg("K"),

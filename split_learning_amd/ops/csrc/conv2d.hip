@@ -39,6 +39,9 @@ at::Tensor conv2d_wino_bwdw(const at::Tensor&, const at::Tensor&, int);
 at::Tensor conv2d_wino_fused(const at::Tensor&, const at::Tensor&,
                              c10::optional<at::Tensor>, int, bool);
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor&, const at::Tensor&, int);
+std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor&,
+                                                   const at::Tensor&,
+                                                   const at::Tensor&, int, int);
 
 // SLK_WINO level for conv_route.h, read once per process
 static int wino_level() {
@@ -300,10 +303,14 @@ struct AtomicStore {
 // out[i] = sum_s slab[s*numel + i]: replaces (zero + atomic accumulate) with
 // streaming slab writes + one reduction pass — at split 64 on a 65 KB output
 // the atomic path was 4M serialized RMWs.
-__global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
-                                   float* __restrict__ out, long numel) {
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < numel;
+// (block, nblocks): the launch's blocks that work on this slab set
+__device__ __forceinline__ void slab_reduce_body(const float* __restrict__ slab,
+                                                 int splits,
+                                                 float* __restrict__ out,
+                                                 long numel, int block,
+                                                 int nblocks) {
+  const long stride = (long)nblocks * blockDim.x;
+  for (long i = (long)block * blockDim.x + threadIdx.x; i < numel;
        i += stride) {
     float s = 0.f;
     for (int k = 0; k < splits; ++k) s += slab[(long)k * numel + i];
@@ -311,12 +318,48 @@ __global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
   }
 }
 
+__global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
+                                   float* __restrict__ out, long numel) {
+  slab_reduce_body(slab, splits, out, numel, blockIdx.x, gridDim.x);
+}
+
+// two independent slab sets in one launch (the gx and gw slabs of a paired
+// conv backward): the first blocks_a blocks sum set a, the rest set b, each
+// element as slab_reduce_kernel sums it
+__global__ void slab_reduce_pair_kernel(const float* __restrict__ slab_a,
+                                        int splits_a, float* __restrict__ out_a,
+                                        long numel_a, int blocks_a,
+                                        const float* __restrict__ slab_b,
+                                        int splits_b, float* __restrict__ out_b,
+                                        long numel_b) {
+  if ((int)blockIdx.x < blocks_a) {
+    slab_reduce_body(slab_a, splits_a, out_a, numel_a, blockIdx.x, blocks_a);
+  } else {
+    slab_reduce_body(slab_b, splits_b, out_b, numel_b, blockIdx.x - blocks_a,
+                     gridDim.x - blocks_a);
+  }
+}
+
+static int slab_reduce_grid(long numel) {
+  return (int)std::min<long>((numel + 255) / 256, 4096);
+}
+
 // shared with wino.hip's ci-/tile-split slabs (declared in torch_util.h)
 void slab_reduce(const float* slab, int splits, float* out, long numel,
                  hipStream_t stream) {
-  const int grid = (int)std::min<long>((numel + 255) / 256, 4096);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid), dim3(256), 0, stream,
-                     slab, splits, out, numel);
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(slab_reduce_grid(numel)),
+                     dim3(256), 0, stream, slab, splits, out, numel);
+}
+
+void slab_reduce_pair(const float* slab_a, int splits_a, float* out_a,
+                      long numel_a, const float* slab_b, int splits_b,
+                      float* out_b, long numel_b, hipStream_t stream) {
+  const int blocks_a = slab_reduce_grid(numel_a);   // 0 for an empty set
+  const int blocks_b = slab_reduce_grid(numel_b);
+  if (blocks_a + blocks_b == 0) return;
+  hipLaunchKernelGGL(slab_reduce_pair_kernel, dim3(blocks_a + blocks_b),
+                     dim3(256), 0, stream, slab_a, splits_a, out_a, numel_a,
+                     blocks_a, slab_b, splits_b, out_b, numel_b);
 }
 
 // slab mode threshold: slab stores beat atomics once MANY splits pile on
@@ -527,6 +570,47 @@ at::Tensor conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x, int KH,
         return AtomicStore{gw, N, accumulate, slab_stride};
       },
       fast);
+}
+
+// SLK_CONV_BWD_PAIR (A/B and bisection only, read once), default 1: a layer
+// whose bwd-data and bwd-weight both take a fused Winograd kernel runs them as
+// one launch (wino_bwd_pair_kernel).  0 is the two-launch sequence.  Every
+// value gives the same bits.
+static bool conv_bwd_pair_enabled() {
+  static const int v = [] {
+    const char* e = std::getenv("SLK_CONV_BWD_PAIR");
+    return e ? atoi(e) : 1;
+  }();
+  return v != 0;
+}
+
+// both gradients of one conv layer.  The routes are conv_route.h's; where
+// they are the two fused Winograd kernels, the pair is a way of LAUNCHING
+// those two routes, not a third route.  Every such pair is launched as one:
+// all seven flagship shapes measured faster paired (B=32, us per layer,
+// separate vs pair: 64ch 32x32 70.0 vs 62.7, 64->128 16x16 48.6 vs 38.9, 128ch
+// 16x16 65.1 vs 51.4, 128->256 8x8 42.8 vs 34.0, 256ch 8x8 66.7 vs 51.1,
+// 256->512 4x4 44.5 vs 31.0, 512ch 4x4 60.9 vs 45.1), so there is no win-set
+// predicate.  An unwanted gradient comes back empty (None in Python).
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>> conv2d_bwd(
+    const at::Tensor& gy, const at::Tensor& x, const at::Tensor& w, int stride,
+    int pad, bool need_gx, bool need_gw) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && gy.dim() == 4);
+  const int H = x.size(2), W = x.size(3), KH = w.size(2), KW = w.size(3);
+  if (need_gx && need_gw && conv_bwd_pair_enabled()) {
+    const ConvShape s = conv_shape(x.size(0), x.size(1), H, W, w.size(0), KH,
+                                   KW, stride, pad);
+    if (s.OH() == gy.size(2) && s.OW() == gy.size(3) &&
+        route_bwd_data(s, wino_level()) == ConvRoute::WinoFused &&
+        route_bwd_weight(s, wino_level()) == ConvRoute::WinoBwdWFused) {
+      auto r = conv2d_bwd_pair(gy, x, w, pad, -1);
+      return {std::get<0>(r), std::get<1>(r)};
+    }
+  }
+  c10::optional<at::Tensor> gx, gw;
+  if (need_gx) gx = conv2d_bwd_data(gy, w, stride, pad, H, W);
+  if (need_gw) gw = conv2d_bwd_weight(gy, x, KH, KW, stride, pad);
+  return {gx, gw};
 }
 
 // which kernel the wrappers above would run for a conv shape, at this

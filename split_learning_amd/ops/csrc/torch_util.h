@@ -31,5 +31,9 @@ static inline int reduce_chunks(long per_channel) {
 // out[i] = sum_s slab[s*numel + i], s in fixed order (conv2d.hip)
 void slab_reduce(const float* slab, int splits, float* out, long numel,
                  hipStream_t stream);
+// the same for two slab sets in one launch; a set with numel 0 has no job
+void slab_reduce_pair(const float* slab_a, int splits_a, float* out_a,
+                      long numel_a, const float* slab_b, int splits_b,
+                      float* out_b, long numel_b, hipStream_t stream);
 
 }  // namespace slk

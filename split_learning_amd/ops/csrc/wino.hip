@@ -22,6 +22,8 @@
 // FUSED kernel (wino_bwdw_fused_kernel).  The fully fused forward
 // (wino_fused_kernel) keeps the transforms in-kernel; routing between the
 // three forms is measured per shape (conv_route.h).
+#include <tuple>
+
 #include "torch_util.h"
 
 namespace slk {
@@ -467,23 +469,24 @@ __device__ __forceinline__ void wino_kstep_mfma(const float* pa,
 // slab_reduce — this fills the chip for small-T/high-Ci shapes
 // whose natural grid is far below one block per CU, and unlike atomicAdd
 // gives the same sum every run.  Slice 0 adds the bias.
+//
+// The body is a device function over a VIRTUAL block index (bx, by, bz) and
+// the caller's two LDS operand arrays, so wino_bwd_pair_kernel can run it next
+// to the bwd-weight body in one grid; wino_fused_kernel passes its blockIdx.
 template <bool FLIP>
-__global__ __launch_bounds__(256, 3) void wino_fused_kernel(
+__device__ __forceinline__ void wino_fused_body(
+    float (&Ul)[WF_OP], float (&Vl)[WF_OP], unsigned bx, unsigned by, unsigned bz,
     const float* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ bias, float* __restrict__ y, int B, int Ci,
     int H, int W, int Co, int OH, int OW, int tH, int tW, int pad,
-    int ci_per, int CW, FastDiv d_thw, FastDiv d_tw) {
-  const int ci_begin = blockIdx.z * ci_per;
+    int ci_per, int CW, const FastDiv& d_thw, const FastDiv& d_tw) {
+  const int ci_begin = bz * ci_per;
   const int ci_end = min(Ci, ci_begin + ci_per);
-  // single-buffer two-barrier loop: double buffering would cost 84 KB of
-  // LDS (1 block/CU); at 42 KB three blocks fit, which is what the
-  // launch bound allows anyway
-  __shared__ __attribute__((aligned(16))) float Ul[WF_OP];   // [co][ci][f]
-  __shared__ __attribute__((aligned(16))) float Vl[WF_OP];   // [t][ci][f]
+  // Ul [co][ci][f], Vl [t][ci][f]
 
   const int T = B * tH * tW;
-  const int co0 = blockIdx.y * WF_CO;
-  const int t0 = blockIdx.x * WF_T;
+  const int co0 = by * WF_CO;
+  const int t0 = bx * WF_T;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -618,12 +621,12 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
       u0[bb] = m[0][bb] + m[1][bb] + m[2][bb];
       u1[bb] = m[1][bb] - m[2][bb] - m[3][bb];
     }
-    const float bv = (bias != nullptr && blockIdx.z == 0) ? bias[co] : 0.f;
+    const float bv = (bias != nullptr && bz == 0) ? bias[co] : 0.f;
     const unsigned b = d_thw.div((unsigned)t);
     const unsigned rem = d_thw.mod((unsigned)t, b);
     const unsigned th = d_tw.div(rem);
     const unsigned tw = d_tw.mod(rem, th);
-    float* yp = y + (long)blockIdx.z * B * Co * OH * OW +
+    float* yp = y + (long)bz * B * Co * OH * OW +
                 ((long)b * Co + co) * OH * OW + (long)th * 2 * OW + tw * 2;
     const float o00 = u0[0] + u0[1] + u0[2] + bv;
     const float o01 = u0[1] - u0[2] - u0[3] + bv;
@@ -634,6 +637,22 @@ __global__ __launch_bounds__(256, 3) void wino_fused_kernel(
     yp[OW] = o10;
     yp[OW + 1] = o11;
   }
+}
+
+template <bool FLIP>
+__global__ __launch_bounds__(256, 3) void wino_fused_kernel(
+    const float* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ bias, float* __restrict__ y, int B, int Ci,
+    int H, int W, int Co, int OH, int OW, int tH, int tW, int pad,
+    int ci_per, int CW, FastDiv d_thw, FastDiv d_tw) {
+  // single-buffer two-barrier loop: double buffering would cost 84 KB of
+  // LDS (1 block/CU); at 42 KB three blocks fit, which is what the
+  // launch bound allows anyway
+  __shared__ __attribute__((aligned(16))) float Ul[WF_OP];   // [co][ci][f]
+  __shared__ __attribute__((aligned(16))) float Vl[WF_OP];   // [t][ci][f]
+  wino_fused_body<FLIP>(Ul, Vl, blockIdx.x, blockIdx.y, blockIdx.z, x, w, bias,
+                        y, B, Ci, H, W, Co, OH, OW, tH, tW, pad, ci_per, CW,
+                        d_thw, d_tw);
 }
 
 at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
@@ -689,17 +708,18 @@ at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
 // applies G^T dU G.  grid.z slices the tile range; slices write per-split
 // slabs (non-atomic) reduced by slab_reduce (the 2.3M-atomicAdd alternative
 // re-creates the split-K atomic pathology measured in round 2).
-__global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
+// As wino_fused_body: (bx, by, bz) is the virtual block index, Gl
+// [co][tloc][f] and Xl [ci][tloc][f] the caller's LDS operand arrays.
+__device__ __forceinline__ void wino_bwdw_fused_body(
+    float (&Gl)[WF_OP], float (&Xl)[WF_OP], unsigned bx, unsigned by, unsigned bz,
     const float* __restrict__ gy, const float* __restrict__ x,
     float* __restrict__ slab, int B, int Ci, int H, int W, int Co, int OH,
-    int OW, int tH, int tW, int pad, int t_per, FastDiv d_thw, FastDiv d_tw) {
-  __shared__ __attribute__((aligned(16))) float Gl[WF_OP];   // [co][tloc][f]
-  __shared__ __attribute__((aligned(16))) float Xl[WF_OP];   // [ci][tloc][f]
-
+    int OW, int tH, int tW, int pad, int t_per, const FastDiv& d_thw,
+    const FastDiv& d_tw) {
   const int T = B * tH * tW;
-  const int ci0 = blockIdx.y * 32;
-  const int co0 = blockIdx.x * 32;
-  const int t_begin = blockIdx.z * t_per;
+  const int ci0 = by * 32;
+  const int co0 = bx * 32;
+  const int t_begin = bz * t_per;
   const int t_end = min(T, t_begin + t_per);
 
   const int tid = threadIdx.x;
@@ -815,7 +835,7 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
       t3[1][bb] = 0.5f * (u[1][bb] - u[2][bb]);
       t3[2][bb] = 0.5f * (u[1][bb] + u[2][bb]) + u[3][bb];
     }
-    float* gp = slab + (long)blockIdx.z * numel + ((long)co * Ci + ci) * 9;
+    float* gp = slab + (long)bz * numel + ((long)co * Ci + ci) * 9;
     #pragma unroll
     for (int r = 0; r < 3; ++r) {
       gp[r * 3 + 0] = t3[r][0] + 0.5f * (t3[r][1] + t3[r][2]);
@@ -823,6 +843,129 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
       gp[r * 3 + 2] = 0.5f * (t3[r][1] + t3[r][2]) + t3[r][3];
     }
   }
+}
+
+__global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
+    const float* __restrict__ gy, const float* __restrict__ x,
+    float* __restrict__ slab, int B, int Ci, int H, int W, int Co, int OH,
+    int OW, int tH, int tW, int pad, int t_per, FastDiv d_thw, FastDiv d_tw) {
+  __shared__ __attribute__((aligned(16))) float Gl[WF_OP];   // [co][tloc][f]
+  __shared__ __attribute__((aligned(16))) float Xl[WF_OP];   // [ci][tloc][f]
+  wino_bwdw_fused_body(Gl, Xl, blockIdx.x, blockIdx.y, blockIdx.z, gy, x, slab,
+                       B, Ci, H, W, Co, OH, OW, tH, tW, pad, t_per, d_thw,
+                       d_tw);
+}
+
+// ---- bwd-data + bwd-weight of one layer in ONE launch -------------------
+// The two are independent given gy, and each alone is sized to about one
+// block per CU of a kernel built for three (profiles/SUMMARY.md round 4: MFMA
+// busy 0.24, waves parked 65-75 % of their life).  As one grid both roles'
+// blocks are resident together and one role's stalls sit under the other's
+// MFMAs.  Each block runs the body of the standalone kernel it replaces over
+// the same virtual (bx, by, bz) — same code, same bits — and the two LDS
+// operand arrays are declared once, so LDS stays 43 008 B and three blocks
+// still fit a CU.
+//
+// Block -> (role, linear index within the role): segregated puts the n_data
+// bwd-data blocks first and the bwd-weight blocks behind them (as
+// wino_wt_in_kernel does); interleaved alternates the roles by block index
+// while both last and gives the longer role the remainder.  Within a role the
+// linear index decodes x-fastest, the order of the standalone kernel's 3-D
+// grid.
+// The default is segregated (measured, tools/conv_bwd_pair_bench.py, the
+// flagship's nine layers at B=32: 410 vs 422 us/step; interleaved gains 0.5 us
+// at the 16x16 layers and loses 7 us at 64ch 32x32, 1.5 us at 256ch 8x8 and
+// 512ch 4x4; separate launches: 526).
+constexpr int WINO_PAIR_INTERLEAVE = 0;
+struct WinoPairData {     // wino_fused_kernel<true>'s arguments
+  const float* x; const float* w; float* y;
+  int B, Ci, H, W, Co, OH, OW, tH, tW, pad, ci_per, CW;
+  FastDiv d_thw, d_tw;
+  int gx, gy, n;          // grid.x, grid.y, blocks
+};
+struct WinoPairWeight {   // wino_bwdw_fused_kernel's arguments
+  const float* gy; const float* x; float* slab;
+  int B, Ci, H, W, Co, OH, OW, tH, tW, pad, t_per;
+  FastDiv d_thw, d_tw;
+  int gx, gy_, n;
+};
+
+__global__ __launch_bounds__(256, 3) void wino_bwd_pair_kernel(
+    WinoPairData d, WinoPairWeight g, int interleave) {
+  __shared__ __attribute__((aligned(16))) float Al[WF_OP];
+  __shared__ __attribute__((aligned(16))) float Bl[WF_OP];
+  // wave-uniform: everything below depends on blockIdx and arguments only
+  const int b = blockIdx.x;
+  bool data;
+  int idx;
+  if (interleave) {
+    const int m = min(d.n, g.n);
+    if (b < 2 * m) {
+      data = (b & 1) == 0;
+      idx = b >> 1;
+    } else {
+      data = d.n > g.n;
+      idx = b - m;
+    }
+  } else {
+    data = b < d.n;
+    idx = data ? b : b - d.n;
+  }
+  if (data) {
+    const int plane = d.gx * d.gy;
+    const int bz = idx / plane;
+    const int r = idx - bz * plane;
+    const int by = r / d.gx;
+    wino_fused_body<true>(Al, Bl, r - by * d.gx, by, bz, d.x, d.w, nullptr,
+                          d.y, d.B, d.Ci, d.H, d.W, d.Co, d.OH, d.OW, d.tH,
+                          d.tW, d.pad, d.ci_per, d.CW, d.d_thw, d.d_tw);
+  } else {
+    const int plane = g.gx * g.gy_;
+    const int bz = idx / plane;
+    const int r = idx - bz * plane;
+    const int by = r / g.gx;
+    wino_bwdw_fused_body(Al, Bl, r - by * g.gx, by, bz, g.gy, g.x, g.slab,
+                         g.B, g.Ci, g.H, g.W, g.Co, g.OH, g.OW, g.tH, g.tW,
+                         g.pad, g.t_per, g.d_thw, g.d_tw);
+  }
+}
+
+// Grid-filling splits of the two fused kernels, shared by their standalone
+// host entries and the pair entry so the slab shapes cannot drift apart
+// (profiles/SUMMARY.md round 2 item 5 was such a drift).  per: the reduction
+// range of one grid.z slice.
+struct WinoSplit { int splits, per; };
+
+// wino_fused_kernel: ci-split so the grid reaches ~1 block/CU (output
+// transform is linear in M: slices store partial y tiles into per-slice
+// slabs; slice count keeps ci chunks at multiples of the CK=8 step).  Co, Ci:
+// the kernel's output and reduction channels (swapped for bwd-data).
+static WinoSplit wino_fused_split(int Co, int Ci, int T) {
+  const long base_blocks = (long)(T / 32) * (Co / 32);
+  int splits = 1;
+  if (base_blocks < 256) {
+    splits = (int)((256 + base_blocks - 1) / base_blocks);
+    const int max_splits = Ci / WF_CK;
+    if (splits > max_splits) splits = max_splits;
+  }
+  const int ci_per = ((Ci / splits + WF_CK - 1) / WF_CK) * WF_CK;
+  splits = (Ci + ci_per - 1) / ci_per;
+  return {splits, ci_per};
+}
+
+// wino_bwdw_fused_kernel: the same over tiles, in steps of 8
+static WinoSplit wino_bwdw_split(int Co, int Ci, int T) {
+  const long base_blocks = (long)(Co / 32) * (Ci / 32);
+  int splits = 1;
+  if (base_blocks < 256) {
+    splits = (int)((256 + base_blocks - 1) / base_blocks);
+    const int max_splits = (T + 7) / 8;
+    if (splits > max_splits) splits = max_splits;
+  }
+  int t_per = ((T / splits + 7) / 8) * 8;
+  if (t_per < 8) t_per = 8;
+  splits = (T + t_per - 1) / t_per;
+  return {splits, t_per};
 }
 
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
@@ -840,16 +983,8 @@ at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
   const int T = B * tH * tW;
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
-  const long base_blocks = (long)(Co / 32) * (Ci / 32);
-  int splits = 1;
-  if (base_blocks < 256) {
-    splits = (int)((256 + base_blocks - 1) / base_blocks);
-    const int max_splits = (T + 7) / 8;
-    if (splits > max_splits) splits = max_splits;
-  }
-  int t_per = ((T / splits + 7) / 8) * 8;
-  if (t_per < 8) t_per = 8;
-  splits = (T + t_per - 1) / t_per;
+  const WinoSplit sp = wino_bwdw_split(Co, Ci, T);
+  const int splits = sp.splits;
 
   auto slab = at::empty({splits, Co, Ci, 3, 3}, x.options());
   FastDiv d_thw, d_tw;
@@ -859,7 +994,7 @@ at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
   hipLaunchKernelGGL(wino_bwdw_fused_kernel, grid, dim3(256), 0, stream,
                      gyc.data_ptr<float>(), xc.data_ptr<float>(),
                      slab.data_ptr<float>(), B, Ci, H, W, Co, OH, OW, tH, tW,
-                     pad, t_per, d_thw, d_tw);
+                     pad, sp.per, d_thw, d_tw);
   if (splits == 1) {
     return slab.view({Co, Ci, 3, 3});
   }
@@ -891,18 +1026,8 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
   // the weight transform runs IN-KERNEL (one (co,ci) pair per thread per
   // staging step) — no wt launch, no 16*Co*Ci frequency tensor
   const int CW = (int)w.size(1);
-  // ci-split so the grid reaches ~1 block/CU (output transform is linear in
-  // M: slices store partial y tiles into per-slice slabs; slice count keeps
-  // ci chunks at multiples of the CK=8 step)
-  const long base_blocks = (long)(T / 32) * (Co / 32);
-  int splits = 1;
-  if (base_blocks < 256) {
-    splits = (int)((256 + base_blocks - 1) / base_blocks);
-    const int max_splits = Ci / WF_CK;
-    if (splits > max_splits) splits = max_splits;
-  }
-  int ci_per = ((Ci / splits + WF_CK - 1) / WF_CK) * WF_CK;
-  splits = (Ci + ci_per - 1) / ci_per;
+  const WinoSplit sp = wino_fused_split(Co, Ci, T);
+  const int splits = sp.splits, ci_per = sp.per;
 
   // every slice covers a non-empty ci range and T, Co are tile multiples, so
   // each slab is written in full
@@ -932,6 +1057,89 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
                 stream);
   }
   return y;
+}
+
+// (bwd-data ci slices, ci per slice, bwd-weight tile slices, tiles per slice)
+// of the layer x [B, Ci, H, W] -> [B, Co, OH, OW]: what
+// conv2d_wino_fused(flip) and conv2d_wino_bwdw_fused use, alone or paired
+std::tuple<int, int, int, int> conv2d_bwd_pair_splits(int B, int Ci, int H,
+                                                      int W, int Co, int pad) {
+  const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
+  const WinoSplit ds = wino_fused_split(Ci, Co, B * (H / 2) * (W / 2));
+  const WinoSplit ws = wino_bwdw_split(Co, Ci, B * (OH / 2) * (OW / 2));
+  return {ds.splits, ds.per, ws.splits, ws.per};
+}
+
+// gx and gw of a 3x3 stride-1 layer from one wino_bwd_pair_kernel launch
+// (plus one reduce launch when either side is split): what
+// conv2d_wino_fused(gy, w, none, 2 - pad, flip) and
+// conv2d_wino_bwdw_fused(gy, x, pad) return, bit for bit.  interleave: the
+// block assignment (see the kernel); < 0 takes the default.
+std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor& gy,
+                                                   const at::Tensor& x,
+                                                   const at::Tensor& w, int pad,
+                                                   int interleave) {
+  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && w.is_cuda() && gy.dim() == 4 &&
+              x.dim() == 4 && w.dim() == 4 && gy.scalar_type() == at::kFloat);
+  TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, "bwd_pair: 3x3 only");
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
+  auto wc = w.contiguous();
+  const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
+  const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
+  TORCH_CHECK(gy.size(0) == B && w.size(0) == Co && w.size(1) == Ci &&
+              OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2 && pad <= 2,
+              "bwd_pair geometry");
+  // bwd-data: a fused conv of gy (Co channels, OH x OW) into Ci channels at
+  // H x W with pad 2 - pad; bwd-weight: tiles of gy
+  const int dtH = H / 2, dtW = W / 2, dT = B * dtH * dtW;
+  const int wtH = OH / 2, wtW = OW / 2, wT = B * wtH * wtW;
+  TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && OH % 2 == 0 && OW % 2 == 0 &&
+              Ci % 32 == 0 && Co % 32 == 0 && dT % 32 == 0,
+              "bwd_pair shape requirements");
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const WinoSplit ds = wino_fused_split(Ci, Co, dT);
+  const WinoSplit ws = wino_bwdw_split(Co, Ci, wT);
+
+  auto gx = at::empty({B, Ci, H, W}, x.options());
+  at::Tensor gx_slab;
+  if (ds.splits > 1) gx_slab = at::empty({ds.splits, B, Ci, H, W}, x.options());
+  auto gw_slab = at::empty({ws.splits, Co, Ci, 3, 3}, x.options());
+
+  WinoPairData d;
+  d.x = gyc.data_ptr<float>();
+  d.w = wc.data_ptr<float>();
+  d.y = ds.splits > 1 ? gx_slab.data_ptr<float>() : gx.data_ptr<float>();
+  d.B = B; d.Ci = Co; d.H = OH; d.W = OW; d.Co = Ci; d.OH = H; d.OW = W;
+  d.tH = dtH; d.tW = dtW; d.pad = 2 - pad; d.ci_per = ds.per; d.CW = Ci;
+  d.d_thw.init(dtH * dtW);
+  d.d_tw.init(dtW);
+  d.gx = dT / 32; d.gy = Ci / 32; d.n = d.gx * d.gy * ds.splits;
+  WinoPairWeight g;
+  g.gy = gyc.data_ptr<float>();
+  g.x = xc.data_ptr<float>();
+  g.slab = gw_slab.data_ptr<float>();
+  g.B = B; g.Ci = Ci; g.H = H; g.W = W; g.Co = Co; g.OH = OH; g.OW = OW;
+  g.tH = wtH; g.tW = wtW; g.pad = pad; g.t_per = ws.per;
+  g.d_thw.init(wtH * wtW);
+  g.d_tw.init(wtW);
+  g.gx = Co / 32; g.gy_ = Ci / 32; g.n = g.gx * g.gy_ * ws.splits;
+  if (interleave < 0) interleave = WINO_PAIR_INTERLEAVE;
+  hipLaunchKernelGGL(wino_bwd_pair_kernel, dim3(d.n + g.n), dim3(256), 0,
+                     stream, d, g, interleave);
+
+  at::Tensor gw = ws.splits > 1 ? at::empty({Co, Ci, 3, 3}, x.options())
+                                : gw_slab.view({Co, Ci, 3, 3});
+  if (ds.splits > 1 || ws.splits > 1) {
+    // a side with one slice was written in place: no job for it
+    slab_reduce_pair(ds.splits > 1 ? gx_slab.data_ptr<float>() : nullptr,
+                     ds.splits, gx.data_ptr<float>(),
+                     ds.splits > 1 ? gx.numel() : 0,
+                     ws.splits > 1 ? gw_slab.data_ptr<float>() : nullptr,
+                     ws.splits, gw.data_ptr<float>(),
+                     ws.splits > 1 ? gw.numel() : 0, stream);
+  }
+  return {gx, gw};
 }
 
 }  // namespace slk

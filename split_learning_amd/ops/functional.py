@@ -155,13 +155,10 @@ class Conv2dFn(Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         gy = gy.contiguous()
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = native().conv2d_bwd_data(gy, weight, ctx.stride, ctx.padding,
-                                          x.shape[2], x.shape[3])
-        if ctx.needs_input_grad[1]:
-            gw = native().conv2d_bwd_weight(gy, x, weight.shape[2], weight.shape[3],
-                                            ctx.stride, ctx.padding)
+        gb = None
+        gx, gw = native().conv2d_bwd(gy, x, weight, ctx.stride, ctx.padding,
+                                     ctx.needs_input_grad[0],
+                                     ctx.needs_input_grad[1])
         if ctx.has_bias and ctx.needs_input_grad[2]:
             if ctx.bias_grad_zero:
                 # conv feeding a TRAINING-mode BatchNorm: the bias gradient is
