@@ -74,6 +74,20 @@ __device__ __forceinline__ float slk_uniform32(uint32_t stream, uint32_t idx) {
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
 
+// ReLU and the max-pool selection rule, one definition each for every kernel
+// that applies them (standalone and fused forms must agree bit for bit).
+// Both keep a NaN, as torch does: fmaxf(NaN, 0) is 0 and NaN > best is false,
+// either of which turns a diverged activation into a healthy-looking zero
+// before the loss's NaN check can see it.
+__device__ __forceinline__ float slk_relu(float v) {
+  return v <= 0.f ? 0.f : v;
+}
+
+// does v replace the running maximum best?  (torch: val > max || isnan(val))
+__device__ __forceinline__ bool slk_pool_takes(float v, float best) {
+  return v > best || v != v;
+}
+
 // Fast integer division by a runtime constant (one 64-bit mul + shift).
 // Valid for dividend < 2^24 and divisor < 2^16 (all tensor-index math here):
 // m = floor(2^40/d)+1; q = (n*m) >> 40 == n/d exactly when n*d < 2^40.

@@ -21,13 +21,13 @@ __global__ void relu_fwd_kernel(const float4* __restrict__ x4, float4* __restric
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 v = x4[i];
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f);
-    v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    v.x = slk_relu(v.x); v.y = slk_relu(v.y);
+    v.z = slk_relu(v.z); v.w = slk_relu(v.w);
     y4[i] = v;
   }
   for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    y[i] = fmaxf(x[i], 0.f);
+    y[i] = slk_relu(x[i]);
 }
 
 __global__ void relu_bwd_kernel(const float* __restrict__ gy,
@@ -35,12 +35,17 @@ __global__ void relu_bwd_kernel(const float* __restrict__ gy,
                                 long n) {
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    gx[i] = y[i] > 0.f ? gy[i] : 0.f;
+    gx[i] = y[i] <= 0.f ? 0.f : gy[i];  // a NaN passes, as in bn_gy_at
 }
 
 at::Tensor relu_fwd(const at::Tensor& x) {
   auto y = at::empty_like(x);
-  const long n = x.numel(), n4 = n / 4;
+  const long n = x.numel();
+  // float4 body only when both pointers are 16-byte aligned (a contiguous
+  // view such as x[1:] is not); otherwise the scalar loop covers everything
+  const bool aligned = ((uintptr_t)x.data_ptr<float>() % 16 == 0) &&
+                       ((uintptr_t)y.data_ptr<float>() % 16 == 0);
+  const long n4 = aligned ? n / 4 : 0;
   auto stream = c10::hip::getCurrentHIPStream().stream();
   hipLaunchKernelGGL(relu_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, stream,
                      (const float4*)x.data_ptr<float>(), (float4*)y.data_ptr<float>(),
@@ -222,10 +227,13 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restric
     const float* xp = x + ((long)bc * H + oh * 2) * W + ow * 2;
     float best = xp[0];
     int bi = 0;
-    if (ow * 2 + 1 < W && xp[1] > best) { best = xp[1]; bi = 1; }
+    if (ow * 2 + 1 < W && slk_pool_takes(xp[1], best)) { best = xp[1]; bi = 1; }
     if (oh * 2 + 1 < H) {
-      if (xp[W] > best) { best = xp[W]; bi = 2; }
-      if (ow * 2 + 1 < W && xp[W + 1] > best) { best = xp[W + 1]; bi = 3; }
+      if (slk_pool_takes(xp[W], best)) { best = xp[W]; bi = 2; }
+      if (ow * 2 + 1 < W && slk_pool_takes(xp[W + 1], best)) {
+        best = xp[W + 1];
+        bi = 3;
+      }
     }
     y[i] = best;
     idx[i] = (uint8_t)bi;

@@ -44,11 +44,15 @@ __global__ void softmax_bwd_kernel(const float* __restrict__ gy,
        row += (long)gridDim.x * waves) {
     const float* gr = gy + row * D;
     const float* yr = y + row * D;
-    float dot = 0.f;
-    for (int d = lane; d < D; d += 64) dot += gr[d] * yr[d];
+    // gy - dot cancels: a near-one-hot row leaves ~1e-4 of its operands, so
+    // dot and the difference stay in double (D/64 terms per lane) and gx is
+    // the rounded result of the saved fp32 y, not of a rounded dot
+    double dot = 0.0;
+    for (int d = lane; d < D; d += 64) dot += (double)gr[d] * (double)yr[d];
     for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
     float* oxr = gx + row * D;
-    for (int d = lane; d < D; d += 64) oxr[d] = yr[d] * (gr[d] - dot);
+    for (int d = lane; d < D; d += 64)
+      oxr[d] = (float)((double)yr[d] * ((double)gr[d] - dot));
   }
 }
 
@@ -81,11 +85,12 @@ at::Tensor softmax_bwd(const at::Tensor& gy, const at::Tensor& y) {
 // One wave per row, each wave summing its rows in order.  A single-block
 // launch (small B) adds the waves' sums in fixed order and stores the loss,
 // so it is the same every run; multi-block launches atomicAdd into a zeroed
-// scalar.
+// DOUBLE scalar (hundreds of float adds into a sum of size `loss` each
+// rounded to its ulp: 7 ulp off at B = 300) that the host casts to float.
 __global__ void ce_fwd_kernel(const float* __restrict__ logits,
                               const int64_t* __restrict__ labels,
                               float* __restrict__ probs, float* __restrict__ loss,
-                              int B, int C) {
+                              double* __restrict__ loss_acc, int B, int C) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int waves = blockDim.x >> 6;
@@ -113,7 +118,7 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
     }
   }
   if (gridDim.x > 1) {
-    if (lane == 0 && acc != 0.f) atomicAdd(loss, acc);
+    if (lane == 0 && acc != 0.f) atomicAdd(loss_acc, (double)acc);
     return;
   }
   if (lane == 0) wave_sum[wid] = acc;
@@ -143,15 +148,26 @@ __global__ void ce_bwd_kernel(const float* __restrict__ probs,
 std::vector<at::Tensor> ce_fwd(const at::Tensor& logits, const at::Tensor& labels) {
   const int B = logits.size(0), C = logits.size(1);
   auto probs = at::empty_like(logits);
-  auto loss = at::zeros({}, logits.options());
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int waves = 4;
   int grid = std::max(1, std::min((B + waves - 1) / waves, 1024));
   if (B <= 256) grid = 1;  // fixed-order in-block sum (see ce_fwd_kernel)
+  if (grid == 1) {
+    auto loss = at::zeros({}, logits.options());
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(1), dim3(64 * waves), 0, stream,
+                       logits.data_ptr<float>(), labels.data_ptr<int64_t>(),
+                       probs.data_ptr<float>(), loss.data_ptr<float>(), nullptr,
+                       B, C);
+    return {loss, probs};
+  }
+  // B > 256 only: the double scalar costs one cast launch that the one-block
+  // path (every batch size the zoo trains or benchmarks with) does not pay
+  auto acc = at::zeros({}, logits.options().dtype(at::kDouble));
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(grid), dim3(64 * waves), 0, stream,
                      logits.data_ptr<float>(), labels.data_ptr<int64_t>(),
-                     probs.data_ptr<float>(), loss.data_ptr<float>(), B, C);
-  return {loss, probs};
+                     probs.data_ptr<float>(), nullptr, acc.data_ptr<double>(), B,
+                     C);
+  return {acc.to(at::kFloat), probs};
 }
 
 at::Tensor ce_bwd(const at::Tensor& probs, const at::Tensor& labels,

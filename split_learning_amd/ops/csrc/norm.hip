@@ -23,7 +23,7 @@ __device__ __forceinline__ float bn_apply(float xv, float m, float is, float g,
                                           float b, bool relu) {
 #pragma clang fp contract(off)
   float v = __builtin_fmaf((xv - m) * is, g, b);
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = slk_relu(v);
   return v;
 }
 
@@ -55,18 +55,18 @@ static inline PoolGeom pool_geom(int H, int W) {
 }
 
 // BN+ReLU of the 2x2 window at xp, then maxpool_fwd_kernel's selection rule:
-// start from position 0, replace on strict > in the order 1, 2, 3.
+// start from position 0, replace on slk_pool_takes in the order 1, 2, 3.
 __device__ __forceinline__ float bn_relu_pool_window(const float* __restrict__ xp,
                                                      int W, float m, float is,
                                                      float g, float b, int& bi) {
   float best = bn_apply(xp[0], m, is, g, b, true);
   bi = 0;
   float v = bn_apply(xp[1], m, is, g, b, true);
-  if (v > best) { best = v; bi = 1; }
+  if (slk_pool_takes(v, best)) { best = v; bi = 1; }
   v = bn_apply(xp[W], m, is, g, b, true);
-  if (v > best) { best = v; bi = 2; }
+  if (slk_pool_takes(v, best)) { best = v; bi = 2; }
   v = bn_apply(xp[W + 1], m, is, g, b, true);
-  if (v > best) { best = v; bi = 3; }
+  if (slk_pool_takes(v, best)) { best = v; bi = 3; }
   return best;
 }
 
@@ -117,14 +117,52 @@ __device__ __forceinline__ void bn_stat_sums(const float* __restrict__ x, int c,
   ts2 = slk_block_sum(s2, scratch);
 }
 
-// mean / invstd / running-stat update of one channel from its float sums
+// mean / invstd / running-stat update of one channel.  sf, s2f are the sums
+// as float (float-cast chunk sums added in float), s, s2 the same sums in
+// double.  E[x^2] - E[x]^2 formed from the float sums cancels mean^2/var
+// leading digits: a channel with mean 1000 and std 1 lost all but two digits
+// of invstd.  The double variance is the yardstick, and taking it always
+// would be the simplest finalize.  It is not taken always because it moves
+// the statistics of well-conditioned channels by an ulp, one ReLU mask flips
+// somewhere in a deep net, and within a few steps a training run no longer
+// reproduces its earlier self (VGG16: gradients 2e-2 apart after one step).
+// So where the float expression lands within BN_KEEP_FLOAT of the double
+// variance, its mean and variance are kept bit for bit; beyond that the
+// double results, rounded once, replace both.  2^-19 is the smallest power of
+// two at which 544 steps of the VGG16 benchmark keep every bit (2^-20 does
+// not).  What this costs: a kept invstd may be up to 2^-20 (1e-6) relative
+// off, about twice the 4-ulp band that the double branch and torch stay
+// within; that happens for mean^2/var from ~5 to ~100, above which the float
+// expression never qualifies.  A NaN sum fails the comparison and stays NaN
+// through the double branch.
+// Only multiplies and subtractions run in double: every block of the
+// one-kernel forward waits on this thread.  1/n comes from the host.
+constexpr double BN_KEEP_FLOAT = 1.0 / 524288.0;
+
+struct BnCount {
+  double inv_n;
+  float n;
+};
+
+static inline BnCount bn_count(long n) {
+  return {1.0 / (double)n, (float)n};
+}
+
 __device__ __forceinline__ void bn_finalize_channel(
-    float s, float s2, float n, int c, float* __restrict__ mean,
-    float* __restrict__ invstd, float* __restrict__ running_mean,
-    float* __restrict__ running_var, float momentum, float eps, float& m_out,
-    float& is_out) {
-  const float m = s / n;
-  const float v = fmaxf(s2 / n - m * m, 0.f);
+    float sf, float s2f, double s, double s2, BnCount cnt, int c,
+    float* __restrict__ mean, float* __restrict__ invstd,
+    float* __restrict__ running_mean, float* __restrict__ running_var,
+    float momentum, float eps, float& m_out, float& is_out) {
+  const float n = cnt.n;
+  float m = sf / n;
+  float v = fmaxf(s2f / n - m * m, 0.f);
+  const double md = s * cnt.inv_n;
+  double vd = s2 * cnt.inv_n - md * md;
+  if (vd < 0.0) vd = 0.0;
+  if (!(fabs((double)v - vd) <= BN_KEEP_FLOAT * vd)) {
+    m = (float)md;
+    v = (float)vd;
+  }
   const float is = rsqrtf(v + eps);
   mean[c] = m;
   invstd[c] = is;
@@ -141,10 +179,11 @@ __device__ __forceinline__ void bn_finalize_channel(
 // kernel that also folds invstd and the running-stat update in-kernel (the
 // previous host-side rsqrt/mul_/add_ chain was 5 extra kernel launches per
 // BN call).
-// slab layout [2][chunks][C]: every slot plainly written (no zero-init, no
-// atomics); the finalize kernel reduces over chunks
+// slab layout [2][chunks][C], double (see bn_finalize_channel; a few KB):
+// every slot plainly written (no zero-init, no atomics); the finalize kernel
+// reduces over chunks
 __global__ void bn_partial_kernel(const float* __restrict__ x,
-                                  float* __restrict__ slab,
+                                  double* __restrict__ slab,
                                   int B, int C, int HW, FastDiv d_hw) {
   __shared__ double scratch[16];
   const int c = blockIdx.x;
@@ -156,30 +195,35 @@ __global__ void bn_partial_kernel(const float* __restrict__ x,
   bn_stat_sums(x, c, lo, hi, C, HW, d_hw, scratch, ts, ts2);
   if (threadIdx.x == 0) {
     const long chunks = gridDim.y;
-    slab[(long)blockIdx.y * C + c] = (float)ts;
-    slab[chunks * C + (long)blockIdx.y * C + c] = (float)ts2;
+    slab[(long)blockIdx.y * C + c] = ts;
+    slab[chunks * C + (long)blockIdx.y * C + c] = ts2;
   }
 }
 
-__global__ void bn_finalize_kernel(const float* __restrict__ slab, int chunks,
+__global__ void bn_finalize_kernel(const double* __restrict__ slab, int chunks,
                                    float* __restrict__ mean,
                                    float* __restrict__ invstd,
                                    float* __restrict__ running_mean,
                                    float* __restrict__ running_var,
-                                   long* __restrict__ nbt, int C, float n,
+                                   long* __restrict__ nbt, int C, BnCount cnt,
                                    float momentum, float eps) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   // num_batches_tracked rides along (was a separate aten long-add launch)
   if (c == 0 && nbt != nullptr) nbt[0] += 1;
   if (c >= C) return;
-  float s = 0.f, s2 = 0.f;
+  double s = 0.0, s2 = 0.0;
+  float sf = 0.f, s2f = 0.f;
   for (int k = 0; k < chunks; ++k) {
-    s += slab[(long)k * C + c];
-    s2 += slab[(long)chunks * C + (long)k * C + c];
+    const double a = slab[(long)k * C + c];
+    const double b = slab[(long)chunks * C + (long)k * C + c];
+    s += a;
+    s2 += b;
+    sf += (float)a;
+    s2f += (float)b;
   }
   float m, is;
-  bn_finalize_channel(s, s2, n, c, mean, invstd, running_mean, running_var,
-                      momentum, eps, m, is);
+  bn_finalize_channel(sf, s2f, s, s2, cnt, c, mean, invstd, running_mean,
+                      running_var, momentum, eps, m, is);
 }
 
 // chunks==1 (B*HW <= 8191: the 8x8-and-smaller VGG layers at B=32): ONE
@@ -193,7 +237,7 @@ __global__ void bn_stats_one_kernel(const float* __restrict__ x,
                                     float* __restrict__ running_var,
                                     long* __restrict__ nbt, int B, int C,
                                     int HW, float momentum, float eps,
-                                    FastDiv d_hw) {
+                                    FastDiv d_hw, BnCount cnt) {
   __shared__ double scratch[16];
   const int c = blockIdx.x;
   if (c == 0 && threadIdx.x == 0 && nbt != nullptr) nbt[0] += 1;
@@ -202,7 +246,7 @@ __global__ void bn_stats_one_kernel(const float* __restrict__ x,
   bn_stat_sums(x, c, 0, total, C, HW, d_hw, scratch, ts, ts2);
   if (threadIdx.x == 0) {
     float m, is;
-    bn_finalize_channel((float)ts, (float)ts2, (float)total, c, mean, invstd,
+    bn_finalize_channel((float)ts, (float)ts2, ts, ts2, cnt, c, mean, invstd,
                         running_mean, running_var, momentum, eps, m, is);
   }
 }
@@ -224,7 +268,7 @@ __global__ void bn_fwd_one_kernel(const float* __restrict__ x,
                                   const float* __restrict__ gamma,
                                   const float* __restrict__ beta, int B, int C,
                                   int HW, float momentum, float eps, bool relu,
-                                  FastDiv d_hw, PoolGeom pg) {
+                                  FastDiv d_hw, PoolGeom pg, BnCount cnt) {
   __shared__ double scratch[16];
   __shared__ float s_stat[2];
   const int c = blockIdx.x;
@@ -233,7 +277,7 @@ __global__ void bn_fwd_one_kernel(const float* __restrict__ x,
   double ts, ts2;
   bn_stat_sums(x, c, 0, total, C, HW, d_hw, scratch, ts, ts2);
   if (threadIdx.x == 0) {
-    bn_finalize_channel((float)ts, (float)ts2, (float)total, c, mean, invstd,
+    bn_finalize_channel((float)ts, (float)ts2, ts, ts2, cnt, c, mean, invstd,
                         running_mean, running_var, momentum, eps, s_stat[0],
                         s_stat[1]);
   }
@@ -484,19 +528,20 @@ std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
                        invstd.data_ptr<float>(), opt_ptr<float>(running_mean),
                        opt_ptr<float>(running_var),
                        opt_ptr<long>(num_batches_tracked),
-                       B, C, HW, (float)momentum, (float)eps, d_hw);
+                       B, C, HW, (float)momentum, (float)eps, d_hw,
+                       bn_count((long)B * HW));
     return {mean, invstd};
   }
-  auto slab = at::empty({2, chunks, C}, x.options());
+  auto slab = at::empty({2, chunks, C}, x.options().dtype(at::kDouble));
   hipLaunchKernelGGL(bn_partial_kernel, dim3(C, chunks), dim3(256), 0, stream,
-                     x.data_ptr<float>(), slab.data_ptr<float>(), B, C, HW,
+                     x.data_ptr<float>(), slab.data_ptr<double>(), B, C, HW,
                      d_hw);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
-                     stream, slab.data_ptr<float>(), chunks,
+                     stream, slab.data_ptr<double>(), chunks,
                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
                      opt_ptr<float>(running_mean), opt_ptr<float>(running_var),
                      opt_ptr<long>(num_batches_tracked),
-                     C, (float)((long)B * HW), (float)momentum, (float)eps);
+                     C, bn_count((long)B * HW), (float)momentum, (float)eps);
   return {mean, invstd};
 }
 
@@ -560,7 +605,8 @@ std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor& x, const at::Tensor& ga
                          opt_ptr<float>(running_mean), opt_ptr<float>(running_var),
                          opt_ptr<long>(num_batches_tracked),
                          gamma.data_ptr<float>(), beta.data_ptr<float>(), B, C,
-                         HW, (float)momentum, (float)eps, relu, d_hw, pg);
+                         HW, (float)momentum, (float)eps, relu, d_hw, pg,
+                         bn_count((long)B * HW));
     };
     if (pool) launch(bn_fwd_one_kernel<true>);
     else launch(bn_fwd_one_kernel<false>);
@@ -854,8 +900,13 @@ __global__ void ln_bwd_dx_kernel(const float* __restrict__ gy,
   __syncthreads();
   float* oxr = gx + row * D;
   for (int d = threadIdx.x; d < D; d += blockDim.x) {
+    // no contraction: fma(gy, gamma, -s_a) keeps the product unrounded while
+    // s_a holds its rounded sum, and the residual times invstd is not small
+    // (D == 1: gx must be exactly 0, came out as invstd * ulp)
+#pragma clang fp contract(off)
     const float xhat = (xr[d] - m) * is;
-    oxr[d] = is * (gr[d] * gamma[d] - s_a - xhat * s_b);
+    const float gg = gr[d] * gamma[d];
+    oxr[d] = is * (gg - s_a - xhat * s_b);
   }
 }
 

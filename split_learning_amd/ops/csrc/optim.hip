@@ -33,10 +33,24 @@ __global__ void sgd_kernel(float* __restrict__ p, float* __restrict__ g,
   }
 }
 
+// AdamW's derived coefficients, formed on the host in double: in float,
+// 1.f - 0.999f is 1.3e-5 (relative) away from 1 - 0.999, and exp_avg_sq
+// carried that factor.
+struct AdamCoef {
+  float omb1, omb2;  // 1 - beta
+  float bc1, bc2;    // 1 - beta^step
+};
+
+static inline AdamCoef adam_coef(double beta1, double beta2, int64_t step) {
+  return {(float)(1.0 - beta1), (float)(1.0 - beta2),
+          (float)(1.0 - std::pow(beta1, (double)step)),
+          (float)(1.0 - std::pow(beta2, (double)step))};
+}
+
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v, long n,
                              float lr, float beta1, float beta2, float eps,
-                             float weight_decay, float bc1, float bc2,
+                             float weight_decay, AdamCoef k,
                              bool zero_after) {
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -44,12 +58,12 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g,
     float pv = p[i] * (1.f - lr * weight_decay);
     const float grad = g[i];
     if (zero_after) g[i] = 0.f;
-    const float mi = beta1 * m[i] + (1.f - beta1) * grad;
-    const float vi = beta2 * v[i] + (1.f - beta2) * grad * grad;
+    const float mi = beta1 * m[i] + k.omb1 * grad;
+    const float vi = beta2 * v[i] + k.omb2 * grad * grad;
     m[i] = mi;
     v[i] = vi;
-    const float mhat = mi / bc1;
-    const float vhat = vi / bc2;
+    const float mhat = mi / k.bc1;
+    const float vhat = vi / k.bc2;
     p[i] = pv - lr * mhat / (sqrtf(vhat) + eps);
   }
 }
@@ -120,7 +134,7 @@ __global__ void sgd_fused_kernel(const long* __restrict__ desc, int n, float lr,
 
 __global__ void adamw_fused_kernel(const long* __restrict__ desc, int n, float lr,
                                    float beta1, float beta2, float eps,
-                                   float weight_decay, float bc1, float bc2,
+                                   float weight_decay, AdamCoef k,
                                    bool zero_after) {
   // (scalar loop: AdamW tensors in this zoo are small; the SGD path above is
   // the hot one and is vectorized)
@@ -141,11 +155,11 @@ __global__ void adamw_fused_kernel(const long* __restrict__ desc, int n, float l
     float pv = p[i] * (1.f - lr * weight_decay);
     const float grad = g[i];
     if (zero_after) g[i] = 0.f;
-    const float mi = beta1 * m[i] + (1.f - beta1) * grad;
-    const float vi = beta2 * v[i] + (1.f - beta2) * grad * grad;
+    const float mi = beta1 * m[i] + k.omb1 * grad;
+    const float vi = beta2 * v[i] + k.omb2 * grad * grad;
     m[i] = mi;
     v[i] = vi;
-    p[i] = pv - lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+    p[i] = pv - lr * (mi / k.bc1) / (sqrtf(vi / k.bc2) + eps);
   }
 }
 
@@ -194,12 +208,11 @@ void adamw_step_fused(const at::Tensor& desc, int64_t n, int64_t chunks,
                       int64_t step, double lr, double beta1, double beta2,
                       double eps, double weight_decay, bool zero_after) {
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const float bc1 = 1.f - powf((float)beta1, (float)step);
-  const float bc2 = 1.f - powf((float)beta2, (float)step);
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   hipLaunchKernelGGL(adamw_fused_kernel, dim3((uint32_t)chunks), dim3(256), 0,
                      stream, desc.data_ptr<int64_t>(), (int)n, (float)lr,
                      (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
-                     bc1, bc2, zero_after);
+                     k, zero_after);
 }
 
 void sgd_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
@@ -220,15 +233,14 @@ void adamw_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                 double lr, double beta1, double beta2, double eps,
                 double weight_decay, bool zero_after) {
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const float bc1 = 1.f - powf((float)beta1, (float)step);
-  const float bc2 = 1.f - powf((float)beta2, (float)step);
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   for (size_t i = 0; i < params.size(); ++i) {
     const long n = params[i].numel();
     hipLaunchKernelGGL(adamw_kernel, dim3(opt_grid(n)), dim3(256), 0, stream,
                        params[i].data_ptr<float>(), grads[i].data_ptr<float>(),
                        ms[i].data_ptr<float>(), vs[i].data_ptr<float>(), n, (float)lr,
                        (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
-                       bc1, bc2, zero_after);
+                       k, zero_after);
   }
 }
 

@@ -1,8 +1,16 @@
-"""Numerics tests: every HIP kernel vs the plain PyTorch fp32 reference.
+"""Numerics tests: the HIP kernels vs the plain PyTorch fp32 reference, one or
+two friendly shapes per op family at a fixed atol/rtol.
 
-All tests are @pytest.mark.gpu (run on a real MI355X via gpurun / at round end).
+All tests are @pytest.mark.gpu (they need a real MI355X).
 Tolerances: the MFMA f32 path is an exact fmaf chain, but summation order
 differs from torch's, so we compare with atol/rtol scaled to operand magnitude.
+
+Not every code path runs here.  The small kernels (optimizers, cross-entropy,
+softmax, LayerNorm, BatchNorm, activations, maxpool, embedding, dropout) are
+tested at their edges (vector body/tail, grid caps, multi-chunk and
+multi-block paths, special values, NaN propagation) against a float64
+reference in tests/test_small_kernels_f64_gpu.py; conv and attention have
+their own modules.
 """
 
 import pytest
