@@ -82,12 +82,14 @@ def build(verbose: bool = True, force: bool = False) -> str:
 
     objs = []
     jobs = []
+    # every header under csrc/ counts as a dependency of every object
+    headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC))
+               if h.endswith(".h")]
     for src in SOURCES:
         sp = os.path.join(CSRC, src)
         op = os.path.join(BUILD_DIR, src.replace("/", "_") + ".o")
         objs.append(op)
-        deps = [sp] + [os.path.join(CSRC, h) for h in (
-            "common.h", "tile_gemm.h", "torch_util.h", "conv_route.h")]
+        deps = [sp] + headers
         if (not force and os.path.exists(op)
                 and all(os.path.getmtime(op) >= os.path.getmtime(d) for d in deps)):
             continue

@@ -572,21 +572,10 @@ at::Tensor conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x, int KH,
       fast);
 }
 
-// SLK_CONV_BWD_PAIR (A/B and bisection only, read once), default 1: a layer
-// whose bwd-data and bwd-weight both take a fused Winograd kernel runs them as
-// one launch (wino_bwd_pair_kernel).  0 is the two-launch sequence.  Every
-// value gives the same bits.
-static bool conv_bwd_pair_enabled() {
-  static const int v = [] {
-    const char* e = std::getenv("SLK_CONV_BWD_PAIR");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0;
-}
-
 // both gradients of one conv layer.  The routes are conv_route.h's; where
 // they are the two fused Winograd kernels, the pair is a way of LAUNCHING
-// those two routes, not a third route.  Every such pair is launched as one:
+// those two routes (wino_bwd_pair_kernel: one launch, the bits of the two),
+// not a third route.  Every such pair is launched as one:
 // all seven flagship shapes measured faster paired (B=32, us per layer,
 // separate vs pair: 64ch 32x32 70.0 vs 62.7, 64->128 16x16 48.6 vs 38.9, 128ch
 // 16x16 65.1 vs 51.4, 128->256 8x8 42.8 vs 34.0, 256ch 8x8 66.7 vs 51.1,
@@ -597,7 +586,7 @@ std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>> conv2d_bwd(
     int pad, bool need_gx, bool need_gw) {
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && gy.dim() == 4);
   const int H = x.size(2), W = x.size(3), KH = w.size(2), KW = w.size(3);
-  if (need_gx && need_gw && conv_bwd_pair_enabled()) {
+  if (need_gx && need_gw) {
     const ConvShape s = conv_shape(x.size(0), x.size(1), H, W, w.size(0), KH,
                                    KW, stride, pad);
     if (s.OH() == gy.size(2) && s.OW() == gy.size(3) &&

@@ -6,33 +6,45 @@
 // y = A^T [ (G g G^T) .* (B^T d B) ] A   per 2x2 output tile (4x4 input
 // patch, overlap 2).  2.25x fewer MACs than direct: the elementwise product
 // becomes 16 frequency-batched GEMMs  M[f] = U[f][Co,Ci] @ V[f][Ci,T]
-// (T = B * OH/2 * OW/2) which run on the existing MFMA tile framework as ONE
-// batched launch.  Unfused (transforms round-trip V/M through HBM; the GEMM's
-// split-K slabs are summed by the output transform), so it
-// wins where the GEMM is compute-dominated — the high-Ci tail of VGG16 —
-// and loses to the direct implicit-GEMM kernel on the big-spatial low-Ci
-// layers where the 4x data inflation of V/M eats the MAC savings
-// (measured routing in conv_route.h; MIOpen's advantage on those layers is a
-// FUSED Winograd with in-kernel transforms).
+// (T = B * OH/2 * OW/2).  Backward-data is the same conv of gy with the
+// 180-degree-rotated, Co/Ci-transposed weights at pad' = KH-1-p (FLIP /
+// flip=true below).  Backward-weight has its own frequency form
+// (dU[f] = (A gy A^T)[f] @ V_x[f]^T, gw = G^T dU G).
 //
-// Backward-data reuses the whole machinery: gx = winograd-conv of gy with
-// the 180-degree-rotated, Co/Ci-transposed weights at pad' = KH-1-p.
-// Backward-weight has its own frequency form (dU[f] = (A gy A^T)[f] @
-// V_x[f]^T, gw = G^T dU G) in both a transform+GEMM pipeline and a fully
-// FUSED kernel (wino_bwdw_fused_kernel).  The fully fused forward
-// (wino_fused_kernel) keeps the transforms in-kernel; routing between the
-// three forms is measured per shape (conv_route.h).
+// The forms in this file; routing between them is measured per shape
+// (conv_route.h):
+//   conv2d_wino             unfused, three launches: wino_wt_in_kernel (both
+//                           operand transforms), the batched MFMA GEMM of
+//                           gemm_f32.hip, wino_out_kernel (sums the GEMM's
+//                           split-K slabs).  V/M round-trip through HBM, so it
+//                           wins where the GEMM is compute-dominated (the
+//                           high-Ci tail of VGG16) and takes the shapes the
+//                           fused kernel's tiles do not divide.
+//   conv2d_wino_bwdw        unfused bwd-weight: wino_gyA_kernel,
+//                           wino_in_kernel, GEMM over the tile axis,
+//                           wino_gw_kernel.
+//   conv2d_wino_fused       wino_fused_kernel<FLIP>: transforms in-kernel, 16-
+//                           frequency MFMA accumulation, no V/M round trip.
+//   conv2d_wino_bwdw_fused  wino_bwdw_fused_kernel, its bwd-weight twin.
+//   conv2d_bwd_pair         wino_bwd_pair_kernel: the bodies of the two fused
+//                           backward kernels in one grid.
+// Every transform's arithmetic is in wino_math.h, once, and each kernel here
+// calls it: that is what keeps the forms bit-identical to each other.  Each
+// fused kernel takes one argument struct (WinoFusedArgs, WinoBwdwArgs) that
+// one host function fills for the standalone entry and for the pair.
 #include <tuple>
+#include <type_traits>
 
 #include "torch_util.h"
+#include "wino_math.h"
 
 namespace slk {
 
 // weight transform U[f] = (G g G^T)[f] over the weight's true dims
 // (Cw0, Cw1) = (w.size(0), w.size(1)); FLIP writes U[f][Cw1][Cw0] with the
 // taps rotated 180 degrees (the bwd-data weight), else U[f][Cw0][Cw1].
-// (block, nblocks): the launch's blocks that work on this transform — the
-// whole grid of wino_wt_kernel, a share of wino_wt_in_kernel's
+// (block, nblocks): the launch's blocks that work on this transform — a share
+// of wino_wt_in_kernel's grid
 template <bool FLIP>
 __device__ __forceinline__ void wino_wt_body(const float* __restrict__ w,
                                              float* __restrict__ U, int Cw0,
@@ -52,7 +64,7 @@ __device__ __forceinline__ void wino_wt_body(const float* __restrict__ w,
     const int r = (int)(i / cols);
     const int co = FLIP ? c : r;   // index into w's dim 0
     const int ci = FLIP ? r : c;   // index into w's dim 1
-    // row a of G g (G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]])
+    // row a of G g
     float t[3];
     #pragma unroll
     for (int b = 0; b < 3; ++b) {
@@ -62,15 +74,11 @@ __device__ __forceinline__ void wino_wt_body(const float* __restrict__ w,
                          (FLIP ? 2 - b : b)];
       const float g2 = w[(((long)co * Cw1 + ci) * 3 + (FLIP ? 0 : 2)) * 3 +
                          (FLIP ? 2 - b : b)];
-      t[b] = a == 0 ? g0
-           : a == 1 ? 0.5f * (g0 + g1 + g2)
-           : a == 2 ? 0.5f * (g0 - g1 + g2)
-           : g2;
+      t[b] = wino_G_row(a, g0, g1, g2);
     }
-    U[((long)(a * 4 + 0) * total) + i] = t[0];
-    U[((long)(a * 4 + 1) * total) + i] = 0.5f * (t[0] + t[1] + t[2]);
-    U[((long)(a * 4 + 2) * total) + i] = 0.5f * (t[0] - t[1] + t[2]);
-    U[((long)(a * 4 + 3) * total) + i] = t[2];
+    const f32x4 u = wino_GgGt_row(t);
+    #pragma unroll
+    for (int b = 0; b < 4; ++b) U[((long)(a * 4 + b) * total) + i] = u[b];
   }
 }
 
@@ -87,44 +95,18 @@ __device__ __forceinline__ void wino_in_body(
        i += stride) {
     const unsigned cc = d_T.div((unsigned)i);
     const unsigned t = d_T.mod((unsigned)i, cc);
-    const unsigned b = d_thw.div(t);
-    const unsigned rem = d_thw.mod(t, b);
-    const unsigned th = d_tw.div(rem);
-    const unsigned tw = d_tw.mod(rem, th);
-    const int ih0 = (int)th * 2 - pad;
-    const int iw0 = (int)tw * 2 - pad;
-    const float* xp = x + ((long)b * Ci + cc) * H * W;
+    const WinoTile tl = wino_tile(t, d_thw, d_tw);
     float d[4][4];
-    #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int ih = ih0 + a;
-      const bool hv = (unsigned)ih < (unsigned)H;
-      #pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const int iw = iw0 + bb;
-        const bool v = hv && (unsigned)iw < (unsigned)W;
-        d[a][bb] = v ? xp[(long)ih * W + iw] : 0.f;
-      }
-    }
-    // B^T d: rows [d0-d2, d1+d2, d2-d1, d1-d3]
+    wino_load_patch(d, x + ((long)tl.b * Ci + cc) * H * W, (int)tl.th * 2 - pad,
+                    (int)tl.tw * 2 - pad, H, W);
     float u[4][4];
-    #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      u[0][bb] = d[0][bb] - d[2][bb];
-      u[1][bb] = d[1][bb] + d[2][bb];
-      u[2][bb] = d[2][bb] - d[1][bb];
-      u[3][bb] = d[1][bb] - d[3][bb];
-    }
+    wino_Bt_d(u, d);
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      const float v0 = u[a][0] - u[a][2];
-      const float v1 = u[a][1] + u[a][2];
-      const float v2 = u[a][2] - u[a][1];
-      const float v3 = u[a][1] - u[a][3];
-      V[((long)(a * 4 + 0) * Ci + cc) * T + t] = v0;
-      V[((long)(a * 4 + 1) * Ci + cc) * T + t] = v1;
-      V[((long)(a * 4 + 2) * Ci + cc) * T + t] = v2;
-      V[((long)(a * 4 + 3) * Ci + cc) * T + t] = v3;
+      const f32x4 v = wino_BtdB_row(u, a);
+      #pragma unroll
+      for (int bb = 0; bb < 4; ++bb)
+        V[((long)(a * 4 + bb) * Ci + cc) * T + t] = v[bb];
     }
   }
 }
@@ -137,19 +119,12 @@ __global__ void wino_in_kernel(const float* __restrict__ x,
                gridDim.x);
 }
 
-template <bool FLIP>
-__global__ void wino_wt_kernel(const float* __restrict__ w,
-                               float* __restrict__ U, int Cw0, int Cw1) {
-  wino_wt_body<FLIP>(w, U, Cw0, Cw1, blockIdx.x, gridDim.x);
-}
-
 // Both operand transforms of conv2d_wino in ONE launch: they are independent
 // (U from w, V from x) and each alone underfills or barely fills the chip for
 // a few microseconds, so as two launches the second waits out the first's
 // drain.  The first in_blocks blocks run the input transform — the short
 // one, so its blocks retire while the weight transform's stream in behind
-// them — the rest the weight transform; each element is computed by the same
-// code as in the separate kernels.
+// them — the rest the weight transform.
 template <bool FLIP>
 __global__ void wino_wt_in_kernel(const float* __restrict__ w,
                                   float* __restrict__ U, int Cw0, int Cw1,
@@ -211,22 +186,15 @@ __global__ __launch_bounds__(256) void wino_out_kernel(
     for (int bb = 0; bb < 4; ++bb) ml[a * 4 + bb][p] = m[bb];
     __syncthreads();
     if (live) {
-      // row oi of A^T m: [m0+m1+m2, m1-m2-m3]; then the same across columns
-      const int oi = a >> 1, oj = a & 1;
-      float u[4];
+      float mf[4][4];
       #pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        u[bb] = oi == 0 ? ml[0 + bb][p] + ml[4 + bb][p] + ml[8 + bb][p]
-                        : ml[4 + bb][p] - ml[8 + bb][p] - ml[12 + bb][p];
-      }
+      for (int f = 0; f < 16; ++f) mf[f >> 2][f & 3] = ml[f][p];
+      const int oi = a >> 1, oj = a & 1;
       const float bv = bias != nullptr ? bias[co] : 0.f;
-      const unsigned b = d_thw.div(t);
-      const unsigned rem = d_thw.mod(t, b);
-      const unsigned th = d_tw.div(rem);
-      const unsigned tw = d_tw.mod(rem, th);
-      float* yp = y + ((long)b * Co + co) * OH * OW + (long)(th * 2 + oi) * OW
-                  + tw * 2 + oj;
-      *yp = oj == 0 ? u[0] + u[1] + u[2] + bv : u[1] - u[2] - u[3] + bv;
+      const WinoTile tl = wino_tile(t, d_thw, d_tw);
+      float* yp = y + ((long)tl.b * Co + co) * OH * OW +
+                  (long)(tl.th * 2 + oi) * OW + tl.tw * 2 + oj;
+      *yp = wino_AtmA(mf, oi, oj, bv);
     }
     __syncthreads();
   }
@@ -234,7 +202,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(
 
 // ---- backward-weight --------------------------------------------------
 // dY arrives per 2x2 output tile; dM = A dY A^T lifts it to the 4x4
-// frequency domain (A = [[1,0],[1,1],[1,-1],[0,-1]]), then
+// frequency domain, then
 // dU[f][Co][Ci] = dM[f][Co,T] @ V_x[f][Ci,T]^T (16 frequency GEMMs over the
 // tile axis — a far better GEMM shape than the direct gather's
 // [Co, Ci*9, B*OH*OW] tall-K formulation), and gw = G^T dU G.
@@ -249,27 +217,16 @@ __global__ void wino_gyA_kernel(const float* __restrict__ gy,
        i += stride) {
     const unsigned co = d_T.div((unsigned)i);
     const unsigned t = d_T.mod((unsigned)i, co);
-    const unsigned b = d_thw.div(t);
-    const unsigned rem = d_thw.mod(t, b);
-    const unsigned th = d_tw.div(rem);
-    const unsigned tw = d_tw.mod(rem, th);
-    const float* gp = gy + ((long)b * Co + co) * OH * OW
-                      + (long)th * 2 * OW + tw * 2;
+    const WinoTile tl = wino_tile(t, d_thw, d_tw);
+    const float* gp = gy + ((long)tl.b * Co + co) * OH * OW
+                      + (long)tl.th * 2 * OW + tl.tw * 2;
     const float g00 = gp[0], g01 = gp[1], g10 = gp[OW], g11 = gp[OW + 1];
-    // rows of A gy (4x2): [g0j], [g0j+g1j], [g0j-g1j], [-g1j]
-    float r0c0 = g00, r0c1 = g01;
-    float r1c0 = g00 + g10, r1c1 = g01 + g11;
-    float r2c0 = g00 - g10, r2c1 = g01 - g11;
-    float r3c0 = -g10, r3c1 = -g11;
-    // columns: dM[a][.] = [c0], [c0+c1], [c0-c1], [-c1]
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      const float c0 = a == 0 ? r0c0 : a == 1 ? r1c0 : a == 2 ? r2c0 : r3c0;
-      const float c1 = a == 0 ? r0c1 : a == 1 ? r1c1 : a == 2 ? r2c1 : r3c1;
-      Wg[((long)(a * 4 + 0) * Co + co) * T + t] = c0;
-      Wg[((long)(a * 4 + 1) * Co + co) * T + t] = c0 + c1;
-      Wg[((long)(a * 4 + 2) * Co + co) * T + t] = c0 - c1;
-      Wg[((long)(a * 4 + 3) * Co + co) * T + t] = -c1;
+      const f32x4 m = wino_AgAt_row(a, g00, g01, g10, g11);
+      #pragma unroll
+      for (int bb = 0; bb < 4; ++bb)
+        Wg[((long)(a * 4 + bb) * Co + co) * T + t] = m[bb];
     }
   }
 }
@@ -283,20 +240,10 @@ __global__ void wino_gw_kernel(const float* __restrict__ dU,
     float u[4][4];
     #pragma unroll
     for (int f = 0; f < 16; ++f) u[f >> 2][f & 3] = dU[(long)f * total + i];
-    // t = G^T u (3x4), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
-    float t[3][4];
+    float g[3][3];
+    wino_GtuG(g, u);
     #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      t[0][b] = u[0][b] + 0.5f * (u[1][b] + u[2][b]);
-      t[1][b] = 0.5f * (u[1][b] - u[2][b]);
-      t[2][b] = 0.5f * (u[1][b] + u[2][b]) + u[3][b];
-    }
-    #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      gw[i * 9 + r * 3 + 0] = t[r][0] + 0.5f * (t[r][1] + t[r][2]);
-      gw[i * 9 + r * 3 + 1] = 0.5f * (t[r][1] - t[r][2]);
-      gw[i * 9 + r * 3 + 2] = 0.5f * (t[r][1] + t[r][2]) + t[r][3];
-    }
+    for (int k = 0; k < 9; ++k) gw[i * 9 + k] = g[k / 3][k % 3];
   }
 }
 
@@ -311,17 +258,35 @@ int conv2d_wino_slabs(int Co, int Ci, int T) {
   return matmul_f32_slab_count(16, Co, T, Ci);
 }
 
-// SLK_WINO_PIPE (A/B and bisection only, read once), default 3: bit 0 = both
-// operand transforms in one launch (wino_wt_in_kernel), bit 1 = the output
-// transform sums the GEMM's split-K slabs.  0 is the five-launch form: wt, in,
-// GEMM, its slab reduce (as matmul_f32 does for every other caller), out.
-// Every value gives the same bits.
-static int wino_pipe_mode() {
-  static int v = [] {
-    const char* e = std::getenv("SLK_WINO_PIPE");
-    return e ? atoi(e) : 3;
-  }();
-  return v;
+// tile grid of a [B, *, OH, OW] output and the dividers that decode an index
+// over it (wino_tile)
+struct WinoTiles {
+  int tH, tW, T;
+  FastDiv d_T, d_thw, d_tw;
+};
+
+static WinoTiles wino_tiles(int B, int OH, int OW) {
+  WinoTiles g;
+  g.tH = OH / 2;
+  g.tW = OW / 2;
+  g.T = B * g.tH * g.tW;
+  g.d_T.init(g.T);
+  g.d_thw.init(g.tH * g.tW);
+  g.d_tw.init(g.tW);
+  return g;
+}
+
+// grid of a 256-thread grid-stride transform kernel over `threads` elements
+static int wino_grid(long threads, int cap) {
+  return (int)std::min<long>((threads + 255) / 256, cap);
+}
+
+// launch(std::true_type or std::false_type): the one place a run-time flip
+// picks a kernel's FLIP instantiation
+template <class Launch>
+static void wino_dispatch_flip(bool flip, Launch&& launch) {
+  if (flip) launch(std::true_type{});
+  else launch(std::false_type{});
 }
 
 // host entry: 3x3 stride-1 conv via F(2x2,3x3); flip=true computes the
@@ -338,63 +303,68 @@ at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(x.size(1) == Ci, "wino: channel mismatch");
   const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
   TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino: even output dims only");
-  const int tH = OH / 2, tW = OW / 2;
-  const int T = B * tH * tW;
+  const WinoTiles g = wino_tiles(B, OH, OW);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  FastDiv d_T, d_thw, d_tw;
-  d_T.init(T);
-  d_thw.init(tH * tW);
-  d_tw.init(tW);
 
-  const int mode = wino_pipe_mode();
   auto U = at::empty({16, Co, Ci}, x.options());
-  auto V = at::empty({16, Ci, T}, x.options());
+  auto V = at::empty({16, Ci, g.T}, x.options());
   // weight transform: thread per (pair, freq row), always over the WEIGHT's
   // own dims (FLIP handles the transpose internally); input transform:
   // thread per (ci, tile)
-  const int wt_grid =
-      (int)std::min<long>(((long)Co * Ci * 4 + 255) / 256, 4096);
-  const int in_grid = (int)std::min<long>(((long)Ci * T + 255) / 256, 8192);
+  const int wt_grid = wino_grid((long)Co * Ci * 4, 4096);
+  const int in_grid = wino_grid((long)Ci * g.T, 8192);
   const int Cw0 = (int)w.size(0), Cw1 = (int)w.size(1);
-  if (mode & 1) {
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(in_grid + wt_grid), dim3(256), 0,
-                         stream, wc.data_ptr<float>(), U.data_ptr<float>(),
-                         Cw0, Cw1, xc.data_ptr<float>(), V.data_ptr<float>(),
-                         B, Ci, H, W, tH, tW, pad, d_T, d_thw, d_tw, in_grid);
-    };
-    if (flip) launch(wino_wt_in_kernel<true>);
-    else launch(wino_wt_in_kernel<false>);
-  } else {
-    if (flip) {
-      hipLaunchKernelGGL(wino_wt_kernel<true>, dim3(wt_grid), dim3(256), 0,
-                         stream, wc.data_ptr<float>(), U.data_ptr<float>(),
-                         Cw0, Cw1);
-    } else {
-      hipLaunchKernelGGL(wino_wt_kernel<false>, dim3(wt_grid), dim3(256), 0,
-                         stream, wc.data_ptr<float>(), U.data_ptr<float>(),
-                         Cw0, Cw1);
-    }
-    hipLaunchKernelGGL(wino_in_kernel, dim3(in_grid), dim3(256), 0, stream,
+  wino_dispatch_flip(flip, [&](auto F) {
+    hipLaunchKernelGGL(wino_wt_in_kernel<decltype(F)::value>,
+                       dim3(in_grid + wt_grid), dim3(256), 0, stream,
+                       wc.data_ptr<float>(), U.data_ptr<float>(), Cw0, Cw1,
                        xc.data_ptr<float>(), V.data_ptr<float>(), B, Ci, H, W,
-                       tH, tW, pad, d_T, d_thw, d_tw);
-  }
+                       g.tH, g.tW, pad, g.d_T, g.d_thw, g.d_tw, in_grid);
+  });
   // M[f] = U[f] @ V[f]: one batched MFMA GEMM launch (batch = 16); its
   // split-K slabs [splits, 16, Co, T] go to the output transform unreduced
-  auto Mm = (mode & 2)
-      ? matmul_f32_slabs(U, V)
-      : matmul_f32(U, V, false, false, c10::nullopt, false).unsqueeze(0);
+  auto Mm = matmul_f32_slabs(U, V);
   auto y = at::empty({B, Co, OH, OW}, x.options());
-  {
-    const long blocks = ((long)Co * T + 63) / 64;   // 64 (co, t) pairs each
-    const int grid = (int)std::min<long>(blocks, 8192);
-    hipLaunchKernelGGL(wino_out_kernel, dim3(grid), dim3(256), 0, stream,
-                       Mm.data_ptr<float>(), (int)Mm.size(0), 16l * Co * T,
-                       y.data_ptr<float>(),
-                       bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                       B, Co, OH, OW, tH, tW, d_T, d_thw, d_tw);
-  }
+  // 64 (co, t) pairs per block
+  const int out_grid = (int)std::min<long>(((long)Co * g.T + 63) / 64, 8192);
+  hipLaunchKernelGGL(wino_out_kernel, dim3(out_grid), dim3(256), 0, stream,
+                     Mm.data_ptr<float>(), (int)Mm.size(0), 16l * Co * g.T,
+                     y.data_ptr<float>(),
+                     bias.has_value() ? bias->data_ptr<float>() : nullptr, B,
+                     Co, OH, OW, g.tH, g.tW, g.d_T, g.d_thw, g.d_tw);
   return y;
+}
+
+at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
+                            int pad) {
+  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
+  const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
+  const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
+  TORCH_CHECK(OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2,
+              "wino_bwdw geometry");
+  TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino_bwdw: even output dims only");
+  const WinoTiles g = wino_tiles(B, OH, OW);
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+
+  auto Wg = at::empty({16, Co, g.T}, x.options());
+  auto Vx = at::empty({16, Ci, g.T}, x.options());
+  hipLaunchKernelGGL(wino_gyA_kernel, dim3(wino_grid((long)Co * g.T, 8192)),
+                     dim3(256), 0, stream, gyc.data_ptr<float>(),
+                     Wg.data_ptr<float>(), B, Co, OH, OW, g.tH, g.tW, g.d_T,
+                     g.d_thw, g.d_tw);
+  hipLaunchKernelGGL(wino_in_kernel, dim3(wino_grid((long)Ci * g.T, 8192)),
+                     dim3(256), 0, stream, xc.data_ptr<float>(),
+                     Vx.data_ptr<float>(), B, Ci, H, W, g.tH, g.tW, pad, g.d_T,
+                     g.d_thw, g.d_tw);
+  // dU[f][Co][Ci] = Wg[f] @ Vx[f]^T : 16 frequency GEMMs, K = tiles
+  auto dU = matmul_f32(Wg, Vx, false, true, c10::nullopt, false);
+  auto gw = at::empty({Co, Ci, 3, 3}, x.options());
+  hipLaunchKernelGGL(wino_gw_kernel, dim3(wino_grid((long)Co * Ci, 4096)),
+                     dim3(256), 0, stream, dU.data_ptr<float>(),
+                     gw.data_ptr<float>(), Co, Ci);
+  return gw;
 }
 
 
@@ -463,6 +433,22 @@ __device__ __forceinline__ void wino_kstep_mfma(const float* pa,
   }
 }
 
+// wino_fused_kernel's arguments: the conv of x [B, Ci, H, W] with w into
+// y [B, Co, OH, OW] over a [B][tH][tW] tile grid.  CW: w.size(1), the stride
+// of w's dim 0 in 3x3 taps (Ci, or Co under FLIP).  Filled by
+// wino_fused_args.
+struct WinoFusedArgs {
+  const float* x;
+  const float* w;
+  const float* bias;   // or nullptr
+  float* y;            // [nz] slabs of B*Co*OH*OW when nz > 1
+  int B, Ci, H, W, Co, OH, OW, tH, tW, pad;
+  int ci_per;          // ci range of one grid.z slice
+  int CW;
+  FastDiv d_thw, d_tw;
+  int nx, ny, nz;      // grid: T / 32, Co / 32, ci slices
+};
+
 // ci_per: the ci-range length per grid.z slice.  The output transform is
 // LINEAR in M, so slices transform their PARTIAL sums, each into its own
 // slab of y (y + blockIdx.z * B*Co*OH*OW), reduced in fixed order by
@@ -476,15 +462,15 @@ __device__ __forceinline__ void wino_kstep_mfma(const float* pa,
 template <bool FLIP>
 __device__ __forceinline__ void wino_fused_body(
     float (&Ul)[WF_OP], float (&Vl)[WF_OP], unsigned bx, unsigned by, unsigned bz,
-    const float* __restrict__ x, const float* __restrict__ w,
-    const float* __restrict__ bias, float* __restrict__ y, int B, int Ci,
-    int H, int W, int Co, int OH, int OW, int tH, int tW, int pad,
-    int ci_per, int CW, const FastDiv& d_thw, const FastDiv& d_tw) {
-  const int ci_begin = bz * ci_per;
-  const int ci_end = min(Ci, ci_begin + ci_per);
+    const WinoFusedArgs& p) {
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ w = p.w;
+  const int H = p.H, W = p.W, Co = p.Co, OH = p.OH, OW = p.OW;
+  const int ci_begin = bz * p.ci_per;
+  const int ci_end = min(p.Ci, ci_begin + p.ci_per);
   // Ul [co][ci][f], Vl [t][ci][f]
 
-  const int T = B * tH * tW;
+  const int T = p.B * p.tH * p.tW;
   const int co0 = by * WF_CO;
   const int t0 = bx * WF_T;
 
@@ -504,14 +490,10 @@ __device__ __forceinline__ void wino_fused_body(
   // V: thread -> one (ci, t) pair: ci = tid >> 5 (8), t = tid & 31 (32)
   const int v_ci = tid >> 5;
   const int v_t = tid & 31;
-  const int tg = t0 + v_t;
-  const unsigned vb = d_thw.div((unsigned)tg);
-  const unsigned vrem = d_thw.mod((unsigned)tg, vb);
-  const unsigned vth = d_tw.div(vrem);
-  const unsigned vtw = d_tw.mod(vrem, vth);
-  const int ih0 = (int)vth * 2 - pad;
-  const int iw0 = (int)vtw * 2 - pad;
-  const long xplane = ((long)vb * Ci + v_ci) * H * W;
+  const WinoTile vt = wino_tile((unsigned)(t0 + v_t), p.d_thw, p.d_tw);
+  const int ih0 = (int)vt.th * 2 - p.pad;
+  const int iw0 = (int)vt.tw * 2 - p.pad;
+  const long xplane = ((long)vt.b * p.Ci + v_ci) * H * W;
   // weights: thread -> one (co, ci) pair (32co x 8ci = 256); the 3x3 taps
   // load raw and transform IN-KERNEL (U = G w G^T, the exact wino_wt math) —
   // the separate wt launch and the 16*Co*Ci frequency tensor's HBM
@@ -531,21 +513,10 @@ __device__ __forceinline__ void wino_fused_body(
   float w8;
 
   auto load_regs = [&](int ci0) {
-    const float* xp = x + xplane + (long)ci0 * H * W;
-    #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int ih = ih0 + a;
-      const bool hv = (unsigned)ih < (unsigned)H;
-      #pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const int iw = iw0 + bb;
-        const bool v = hv && (unsigned)iw < (unsigned)W;
-        d[a][bb] = v ? xp[(long)ih * W + iw] : 0.f;
-      }
-    }
+    wino_load_patch(d, x + xplane + (long)ci0 * H * W, ih0, iw0, H, W);
     const long wbase = FLIP
-        ? ((long)(ci0 + w_ci) * CW + (co0 + w_co)) * 9
-        : ((long)(co0 + w_co) * CW + (ci0 + w_ci)) * 9;
+        ? ((long)(ci0 + w_ci) * p.CW + (co0 + w_co)) * 9
+        : ((long)(co0 + w_co) * p.CW + (ci0 + w_ci)) * 9;
     using f32x4u = __attribute__((ext_vector_type(4), aligned(4))) float;
     wq0 = *reinterpret_cast<const f32x4u*>(w + wbase);
     wq1 = *reinterpret_cast<const f32x4u*>(w + wbase + 4);
@@ -554,42 +525,26 @@ __device__ __forceinline__ void wino_fused_body(
 
   auto store_stage = [&]() {
     float u[4][4];
-    #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      u[0][bb] = d[0][bb] - d[2][bb];
-      u[1][bb] = d[1][bb] + d[2][bb];
-      u[2][bb] = d[2][bb] - d[1][bb];
-      u[3][bb] = d[1][bb] - d[3][bb];
-    }
+    wino_Bt_d(u, d);
     f32x4* vp = reinterpret_cast<f32x4*>(&Vl[v_t * WF_RS + v_ci * WF_KS]);
     #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      vp[a] = f32x4{u[a][0] - u[a][2], u[a][1] + u[a][2],
-                    u[a][2] - u[a][1], u[a][1] - u[a][3]};
-    }
-    // U = G w G^T for this thread's (co, ci) pair — same op order as
-    // wino_wt_kernel, so the result is bit-identical to the staged path
+    for (int a = 0; a < 4; ++a) vp[a] = wino_BtdB_row(u, a);
+    // U = G w G^T for this thread's (co, ci) pair — the expressions of
+    // wino_wt_body (wino_math.h), so the result is bit-identical to the
+    // staged path
     const float raw[9] = {wq0[0], wq0[1], wq0[2], wq0[3], wq1[0],
                           wq1[1], wq1[2], wq1[3], w8};
     float wr[9];
     #pragma unroll
     for (int k = 0; k < 9; ++k) wr[k] = raw[FLIP ? 8 - k : k];
-    float t0[3], t1[3], t2[3], t3[3];
-    #pragma unroll
-    for (int bb = 0; bb < 3; ++bb) {
-      const float g0 = wr[bb], g1 = wr[3 + bb], g2 = wr[6 + bb];
-      t0[bb] = g0;
-      t1[bb] = 0.5f * (g0 + g1 + g2);
-      t2[bb] = 0.5f * (g0 - g1 + g2);
-      t3[bb] = g2;
-    }
-    const float* tr[4] = {t0, t1, t2, t3};
     f32x4* up = reinterpret_cast<f32x4*>(&Ul[w_co * WF_RS + w_ci * WF_KS]);
     #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      const float* t = tr[a];
-      up[a] = f32x4{t[0], 0.5f * (t[0] + t[1] + t[2]),
-                    0.5f * (t[0] - t[1] + t[2]), t[2]};
+      float t[3];
+      #pragma unroll
+      for (int bb = 0; bb < 3; ++bb)
+        t[bb] = wino_G_row(a, wr[bb], wr[3 + bb], wr[6 + bb]);
+      up[a] = wino_GgGt_row(t);
     }
   };
 
@@ -615,23 +570,15 @@ __device__ __forceinline__ void wino_fused_body(
     float m[4][4];
     #pragma unroll
     for (int f = 0; f < 16; ++f) m[f >> 2][f & 3] = acc[f][i];
-    float u0[4], u1[4];
-    #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      u0[bb] = m[0][bb] + m[1][bb] + m[2][bb];
-      u1[bb] = m[1][bb] - m[2][bb] - m[3][bb];
-    }
-    const float bv = (bias != nullptr && bz == 0) ? bias[co] : 0.f;
-    const unsigned b = d_thw.div((unsigned)t);
-    const unsigned rem = d_thw.mod((unsigned)t, b);
-    const unsigned th = d_tw.div(rem);
-    const unsigned tw = d_tw.mod(rem, th);
-    float* yp = y + (long)bz * B * Co * OH * OW +
-                ((long)b * Co + co) * OH * OW + (long)th * 2 * OW + tw * 2;
-    const float o00 = u0[0] + u0[1] + u0[2] + bv;
-    const float o01 = u0[1] - u0[2] - u0[3] + bv;
-    const float o10 = u1[0] + u1[1] + u1[2] + bv;
-    const float o11 = u1[1] - u1[2] - u1[3] + bv;
+    const float bv = (p.bias != nullptr && bz == 0) ? p.bias[co] : 0.f;
+    const WinoTile tl = wino_tile((unsigned)t, p.d_thw, p.d_tw);
+    float* yp = p.y + (long)bz * p.B * Co * OH * OW +
+                ((long)tl.b * Co + co) * OH * OW + (long)tl.th * 2 * OW +
+                tl.tw * 2;
+    const float o00 = wino_AtmA(m, 0, 0, bv);
+    const float o01 = wino_AtmA(m, 0, 1, bv);
+    const float o10 = wino_AtmA(m, 1, 0, bv);
+    const float o11 = wino_AtmA(m, 1, 1, bv);
     yp[0] = o00;
     yp[1] = o01;
     yp[OW] = o10;
@@ -640,66 +587,27 @@ __device__ __forceinline__ void wino_fused_body(
 }
 
 template <bool FLIP>
-__global__ __launch_bounds__(256, 3) void wino_fused_kernel(
-    const float* __restrict__ x, const float* __restrict__ w,
-    const float* __restrict__ bias, float* __restrict__ y, int B, int Ci,
-    int H, int W, int Co, int OH, int OW, int tH, int tW, int pad,
-    int ci_per, int CW, FastDiv d_thw, FastDiv d_tw) {
+__global__ __launch_bounds__(256, 3) void wino_fused_kernel(WinoFusedArgs p) {
   // single-buffer two-barrier loop: double buffering would cost 84 KB of
   // LDS (1 block/CU); at 42 KB three blocks fit, which is what the
   // launch bound allows anyway
   __shared__ __attribute__((aligned(16))) float Ul[WF_OP];   // [co][ci][f]
   __shared__ __attribute__((aligned(16))) float Vl[WF_OP];   // [t][ci][f]
-  wino_fused_body<FLIP>(Ul, Vl, blockIdx.x, blockIdx.y, blockIdx.z, x, w, bias,
-                        y, B, Ci, H, W, Co, OH, OW, tH, tW, pad, ci_per, CW,
-                        d_thw, d_tw);
+  wino_fused_body<FLIP>(Ul, Vl, blockIdx.x, blockIdx.y, blockIdx.z, p);
 }
 
-at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
-                            int pad) {
-  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
-  auto gyc = gy.contiguous();
-  auto xc = x.contiguous();
-  const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
-  const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
-  TORCH_CHECK(OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2,
-              "wino_bwdw geometry");
-  TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino_bwdw: even output dims only");
-  const int tH = OH / 2, tW = OW / 2;
-  const int T = B * tH * tW;
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  FastDiv d_T, d_thw, d_tw;
-  d_T.init(T);
-  d_thw.init(tH * tW);
-  d_tw.init(tW);
-
-  auto Wg = at::empty({16, Co, T}, x.options());
-  auto Vx = at::empty({16, Ci, T}, x.options());
-  {
-    const long tot = (long)Co * T;
-    const int grid = (int)std::min<long>((tot + 255) / 256, 8192);
-    hipLaunchKernelGGL(wino_gyA_kernel, dim3(grid), dim3(256), 0, stream,
-                       gyc.data_ptr<float>(), Wg.data_ptr<float>(), B, Co, OH,
-                       OW, tH, tW, d_T, d_thw, d_tw);
-  }
-  {
-    const long tot = (long)Ci * T;
-    const int grid = (int)std::min<long>((tot + 255) / 256, 8192);
-    hipLaunchKernelGGL(wino_in_kernel, dim3(grid), dim3(256), 0, stream,
-                       xc.data_ptr<float>(), Vx.data_ptr<float>(), B, Ci, H, W,
-                       tH, tW, pad, d_T, d_thw, d_tw);
-  }
-  // dU[f][Co][Ci] = Wg[f] @ Vx[f]^T : 16 frequency GEMMs, K = tiles
-  auto dU = matmul_f32(Wg, Vx, false, true, c10::nullopt, false);
-  auto gw = at::empty({Co, Ci, 3, 3}, x.options());
-  {
-    const long tot = (long)Co * Ci;
-    const int grid = (int)std::min<long>((tot + 255) / 256, 4096);
-    hipLaunchKernelGGL(wino_gw_kernel, dim3(grid), dim3(256), 0, stream,
-                       dU.data_ptr<float>(), gw.data_ptr<float>(), Co, Ci);
-  }
-  return gw;
-}
+// wino_bwdw_fused_kernel's arguments: gw slabs [nz][Co][Ci][3][3] of the
+// layer x [B, Ci, H, W] -> gy [B, Co, OH, OW] over gy's [B][tH][tW] tile grid.
+// Filled by wino_bwdw_args.
+struct WinoBwdwArgs {
+  const float* gy;
+  const float* x;
+  float* slab;
+  int B, Ci, H, W, Co, OH, OW, tH, tW, pad;
+  int t_per;           // tile range of one grid.z slice
+  FastDiv d_thw, d_tw;
+  int nx, ny, nz;      // grid: Co / 32, Ci / 32, tile slices
+};
 
 // ---- fused backward-weight --------------------------------------------
 // Twin of wino_fused_kernel with the TILE axis as the reduction: block owns
@@ -712,15 +620,15 @@ at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
 // [co][tloc][f] and Xl [ci][tloc][f] the caller's LDS operand arrays.
 __device__ __forceinline__ void wino_bwdw_fused_body(
     float (&Gl)[WF_OP], float (&Xl)[WF_OP], unsigned bx, unsigned by, unsigned bz,
-    const float* __restrict__ gy, const float* __restrict__ x,
-    float* __restrict__ slab, int B, int Ci, int H, int W, int Co, int OH,
-    int OW, int tH, int tW, int pad, int t_per, const FastDiv& d_thw,
-    const FastDiv& d_tw) {
-  const int T = B * tH * tW;
+    const WinoBwdwArgs& p) {
+  const float* __restrict__ gy = p.gy;
+  const float* __restrict__ x = p.x;
+  const int Ci = p.Ci, H = p.H, W = p.W, Co = p.Co, OH = p.OH, OW = p.OW;
+  const int T = p.B * p.tH * p.tW;
   const int ci0 = by * 32;
   const int co0 = bx * 32;
-  const int t_begin = bz * t_per;
-  const int t_end = min(T, t_begin + t_per);
+  const int t_begin = bz * p.t_per;
+  const int t_end = min(T, t_begin + p.t_per);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -745,64 +653,27 @@ __device__ __forceinline__ void wino_bwdw_fused_body(
     const int t = t0 + s_t;
     const int tc = t < T ? t : T - 1;
     const bool tv = t < t_end;
-    const unsigned b = d_thw.div((unsigned)tc);
-    const unsigned rem = d_thw.mod((unsigned)tc, b);
-    const unsigned th = d_tw.div(rem);
-    const unsigned tw = d_tw.mod(rem, th);
-    {
-      const float* gp = gy + ((long)b * Co + co0 + s_ch) * OH * OW
-                        + (long)th * 2 * OW + tw * 2;
-      gg[0][0] = tv ? gp[0] : 0.f;
-      gg[0][1] = tv ? gp[1] : 0.f;
-      gg[1][0] = tv ? gp[OW] : 0.f;
-      gg[1][1] = tv ? gp[OW + 1] : 0.f;
-    }
-    {
-      const int ih0 = (int)th * 2 - pad;
-      const int iw0 = (int)tw * 2 - pad;
-      const float* xp = x + ((long)b * Ci + ci0 + s_ch) * H * W;
-      #pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int ih = ih0 + a;
-        const bool hv = tv && (unsigned)ih < (unsigned)H;
-        #pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int iw = iw0 + bb;
-          const bool v = hv && (unsigned)iw < (unsigned)W;
-          xd[a][bb] = v ? xp[(long)ih * W + iw] : 0.f;
-        }
-      }
-    }
+    const WinoTile tl = wino_tile((unsigned)tc, p.d_thw, p.d_tw);
+    const float* gp = gy + ((long)tl.b * Co + co0 + s_ch) * OH * OW
+                      + (long)tl.th * 2 * OW + tl.tw * 2;
+    gg[0][0] = tv ? gp[0] : 0.f;
+    gg[0][1] = tv ? gp[1] : 0.f;
+    gg[1][0] = tv ? gp[OW] : 0.f;
+    gg[1][1] = tv ? gp[OW + 1] : 0.f;
+    wino_load_patch(xd, x + ((long)tl.b * Ci + ci0 + s_ch) * H * W,
+                    (int)tl.th * 2 - p.pad, (int)tl.tw * 2 - p.pad, H, W, tv);
   };
 
   auto store_stage = [&]() {
-    // dM = A gy A^T (A = [[1,0],[1,1],[1,-1],[0,-1]])
-    const float r0c0 = gg[0][0], r0c1 = gg[0][1];
-    const float r1c0 = gg[0][0] + gg[1][0], r1c1 = gg[0][1] + gg[1][1];
-    const float r2c0 = gg[0][0] - gg[1][0], r2c1 = gg[0][1] - gg[1][1];
-    const float r3c0 = -gg[1][0], r3c1 = -gg[1][1];
     f32x4* gp4 = reinterpret_cast<f32x4*>(&Gl[s_ch * WF_RS + s_t * WF_KS]);
     f32x4* xp4 = reinterpret_cast<f32x4*>(&Xl[s_ch * WF_RS + s_t * WF_KS]);
     #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const float c0 = a == 0 ? r0c0 : a == 1 ? r1c0 : a == 2 ? r2c0 : r3c0;
-      const float c1 = a == 0 ? r0c1 : a == 1 ? r1c1 : a == 2 ? r2c1 : r3c1;
-      gp4[a] = f32x4{c0, c0 + c1, c0 - c1, -c1};
-    }
-    // B^T d B
+    for (int a = 0; a < 4; ++a)
+      gp4[a] = wino_AgAt_row(a, gg[0][0], gg[0][1], gg[1][0], gg[1][1]);
     float u[4][4];
+    wino_Bt_d(u, xd);
     #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      u[0][bb] = xd[0][bb] - xd[2][bb];
-      u[1][bb] = xd[1][bb] + xd[2][bb];
-      u[2][bb] = xd[2][bb] - xd[1][bb];
-      u[3][bb] = xd[1][bb] - xd[3][bb];
-    }
-    #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      xp4[a] = f32x4{u[a][0] - u[a][2], u[a][1] + u[a][2],
-                     u[a][2] - u[a][1], u[a][1] - u[a][3]};
-    }
+    for (int a = 0; a < 4; ++a) xp4[a] = wino_BtdB_row(u, a);
   };
 
   const float* pa = &Gl[(wco + frag_c) * WF_RS + frag_r * WF_KS];
@@ -828,32 +699,19 @@ __device__ __forceinline__ void wino_bwdw_fused_body(
     float u[4][4];
     #pragma unroll
     for (int f = 0; f < 16; ++f) u[f >> 2][f & 3] = acc[f][i];
-    float t3[3][4];
+    float g[3][3];
+    wino_GtuG(g, u);
+    float* gp = p.slab + (long)bz * numel + ((long)co * Ci + ci) * 9;
     #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      t3[0][bb] = u[0][bb] + 0.5f * (u[1][bb] + u[2][bb]);
-      t3[1][bb] = 0.5f * (u[1][bb] - u[2][bb]);
-      t3[2][bb] = 0.5f * (u[1][bb] + u[2][bb]) + u[3][bb];
-    }
-    float* gp = slab + (long)bz * numel + ((long)co * Ci + ci) * 9;
-    #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      gp[r * 3 + 0] = t3[r][0] + 0.5f * (t3[r][1] + t3[r][2]);
-      gp[r * 3 + 1] = 0.5f * (t3[r][1] - t3[r][2]);
-      gp[r * 3 + 2] = 0.5f * (t3[r][1] + t3[r][2]) + t3[r][3];
-    }
+    for (int k = 0; k < 9; ++k) gp[k] = g[k / 3][k % 3];
   }
 }
 
 __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
-    const float* __restrict__ gy, const float* __restrict__ x,
-    float* __restrict__ slab, int B, int Ci, int H, int W, int Co, int OH,
-    int OW, int tH, int tW, int pad, int t_per, FastDiv d_thw, FastDiv d_tw) {
+    WinoBwdwArgs p) {
   __shared__ __attribute__((aligned(16))) float Gl[WF_OP];   // [co][tloc][f]
   __shared__ __attribute__((aligned(16))) float Xl[WF_OP];   // [ci][tloc][f]
-  wino_bwdw_fused_body(Gl, Xl, blockIdx.x, blockIdx.y, blockIdx.z, gy, x, slab,
-                       B, Ci, H, W, Co, OH, OW, tH, tW, pad, t_per, d_thw,
-                       d_tw);
+  wino_bwdw_fused_body(Gl, Xl, blockIdx.x, blockIdx.y, blockIdx.z, p);
 }
 
 // ---- bwd-data + bwd-weight of one layer in ONE launch -------------------
@@ -862,9 +720,9 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
 // busy 0.24, waves parked 65-75 % of their life).  As one grid both roles'
 // blocks are resident together and one role's stalls sit under the other's
 // MFMAs.  Each block runs the body of the standalone kernel it replaces over
-// the same virtual (bx, by, bz) — same code, same bits — and the two LDS
-// operand arrays are declared once, so LDS stays 43 008 B and three blocks
-// still fit a CU.
+// the same virtual (bx, by, bz) and the same argument struct — same code, same
+// bits — and the two LDS operand arrays are declared once, so LDS stays
+// 43 008 B and three blocks still fit a CU.
 //
 // Block -> (role, linear index within the role): segregated puts the n_data
 // bwd-data blocks first and the bwd-weight blocks behind them (as
@@ -877,63 +735,44 @@ __global__ __launch_bounds__(256, 2) void wino_bwdw_fused_kernel(
 // at the 16x16 layers and loses 7 us at 64ch 32x32, 1.5 us at 256ch 8x8 and
 // 512ch 4x4; separate launches: 526).
 constexpr int WINO_PAIR_INTERLEAVE = 0;
-struct WinoPairData {     // wino_fused_kernel<true>'s arguments
-  const float* x; const float* w; float* y;
-  int B, Ci, H, W, Co, OH, OW, tH, tW, pad, ci_per, CW;
-  FastDiv d_thw, d_tw;
-  int gx, gy, n;          // grid.x, grid.y, blocks
-};
-struct WinoPairWeight {   // wino_bwdw_fused_kernel's arguments
-  const float* gy; const float* x; float* slab;
-  int B, Ci, H, W, Co, OH, OW, tH, tW, pad, t_per;
-  FastDiv d_thw, d_tw;
-  int gx, gy_, n;
-};
 
+// d: wino_fused_kernel<true>'s arguments, g: wino_bwdw_fused_kernel's
 __global__ __launch_bounds__(256, 3) void wino_bwd_pair_kernel(
-    WinoPairData d, WinoPairWeight g, int interleave) {
+    WinoFusedArgs d, WinoBwdwArgs g, int interleave) {
   __shared__ __attribute__((aligned(16))) float Al[WF_OP];
   __shared__ __attribute__((aligned(16))) float Bl[WF_OP];
   // wave-uniform: everything below depends on blockIdx and arguments only
   const int b = blockIdx.x;
+  const int dn = d.nx * d.ny * d.nz, gn = g.nx * g.ny * g.nz;
   bool data;
   int idx;
   if (interleave) {
-    const int m = min(d.n, g.n);
+    const int m = min(dn, gn);
     if (b < 2 * m) {
       data = (b & 1) == 0;
       idx = b >> 1;
     } else {
-      data = d.n > g.n;
+      data = dn > gn;
       idx = b - m;
     }
   } else {
-    data = b < d.n;
-    idx = data ? b : b - d.n;
+    data = b < dn;
+    idx = data ? b : b - dn;
   }
-  if (data) {
-    const int plane = d.gx * d.gy;
-    const int bz = idx / plane;
-    const int r = idx - bz * plane;
-    const int by = r / d.gx;
-    wino_fused_body<true>(Al, Bl, r - by * d.gx, by, bz, d.x, d.w, nullptr,
-                          d.y, d.B, d.Ci, d.H, d.W, d.Co, d.OH, d.OW, d.tH,
-                          d.tW, d.pad, d.ci_per, d.CW, d.d_thw, d.d_tw);
-  } else {
-    const int plane = g.gx * g.gy_;
-    const int bz = idx / plane;
-    const int r = idx - bz * plane;
-    const int by = r / g.gx;
-    wino_bwdw_fused_body(Al, Bl, r - by * g.gx, by, bz, g.gy, g.x, g.slab,
-                         g.B, g.Ci, g.H, g.W, g.Co, g.OH, g.OW, g.tH, g.tW,
-                         g.pad, g.t_per, g.d_thw, g.d_tw);
-  }
+  const int nx = data ? d.nx : g.nx;
+  const int plane = nx * (data ? d.ny : g.ny);
+  const int bz = idx / plane;
+  const int r = idx - bz * plane;
+  const int by = r / nx;
+  const int bx = r - by * nx;
+  if (data) wino_fused_body<true>(Al, Bl, bx, by, bz, d);
+  else wino_bwdw_fused_body(Al, Bl, bx, by, bz, g);
 }
 
-// Grid-filling splits of the two fused kernels, shared by their standalone
-// host entries and the pair entry so the slab shapes cannot drift apart
-// (profiles/SUMMARY.md round 2 item 5 was such a drift).  per: the reduction
-// range of one grid.z slice.
+// Grid-filling splits of the two fused kernels, computed where their argument
+// structs are filled, so the slab shapes of the standalone entries and of the
+// pair cannot drift apart (profiles/SUMMARY.md round 2 item 5 was such a
+// drift).  per: the reduction range of one grid.z slice.
 struct WinoSplit { int splits, per; };
 
 // wino_fused_kernel: ci-split so the grid reaches ~1 block/CU (output
@@ -968,38 +807,76 @@ static WinoSplit wino_bwdw_split(int Co, int Ci, int T) {
   return {splits, t_per};
 }
 
+// Geometry, split and grid of wino_fused_kernel for a conv of [B, Ci, H, W]
+// into Co channels at padding `pad`, in the KERNEL's roles; CW = w.size(1).
+// The pointers are the caller's to fill.  Shape requirements: Co % 32 == 0,
+// T % 32 == 0, Ci % 8 == 0.  who: the public entry, for the error text.
+static WinoFusedArgs wino_fused_args(int B, int Ci, int H, int W, int Co,
+                                     int pad, int CW, const char* who) {
+  WinoFusedArgs a{};
+  a.B = B; a.Ci = Ci; a.H = H; a.W = W; a.Co = Co; a.pad = pad; a.CW = CW;
+  a.OH = H + 2 * pad - 2;
+  a.OW = W + 2 * pad - 2;
+  const WinoTiles g = wino_tiles(B, a.OH, a.OW);
+  TORCH_CHECK(Co % 32 == 0 && g.T % 32 == 0 && Ci % 8 == 0 && a.OH % 2 == 0 &&
+              a.OW % 2 == 0 && g.T > 0, who, " shape requirements");
+  a.tH = g.tH; a.tW = g.tW; a.d_thw = g.d_thw; a.d_tw = g.d_tw;
+  const WinoSplit sp = wino_fused_split(Co, Ci, g.T);
+  a.ci_per = sp.per;
+  a.nx = g.T / 32; a.ny = Co / 32; a.nz = sp.splits;
+  return a;
+}
+
+// the bwd-data conv of the layer x [B, Ci, H, W] -> [B, Co, OH, OW] as
+// wino_fused_kernel<true> sees it: gy's Co channels at OH x OW into Ci
+// channels at H x W with padding 2 - pad; w stays [Co, Ci, 3, 3]
+static WinoFusedArgs wino_bwd_data_args(int B, int Ci, int H, int W, int Co,
+                                        int pad, const char* who) {
+  return wino_fused_args(B, Co, H + 2 * pad - 2, W + 2 * pad - 2, Ci, 2 - pad,
+                         Ci, who);
+}
+
+// the same for wino_bwdw_fused_kernel and the layer x [B, Ci, H, W] ->
+// [B, Co, OH, OW].  Shape requirements: Co % 32 == 0, Ci % 32 == 0.
+static WinoBwdwArgs wino_bwdw_args(int B, int Ci, int H, int W, int Co, int pad,
+                                   const char* who) {
+  WinoBwdwArgs a{};
+  a.B = B; a.Ci = Ci; a.H = H; a.W = W; a.Co = Co; a.pad = pad;
+  a.OH = H + 2 * pad - 2;
+  a.OW = W + 2 * pad - 2;
+  TORCH_CHECK(a.OH % 2 == 0 && a.OW % 2 == 0 && Co % 32 == 0 && Ci % 32 == 0 &&
+              Co > 0 && Ci > 0, who, " shape requirements");
+  const WinoTiles g = wino_tiles(B, a.OH, a.OW);
+  a.tH = g.tH; a.tW = g.tW; a.d_thw = g.d_thw; a.d_tw = g.d_tw;
+  const WinoSplit sp = wino_bwdw_split(Co, Ci, g.T);
+  a.t_per = sp.per;
+  a.nx = Co / 32; a.ny = Ci / 32; a.nz = sp.splits;
+  return a;
+}
+
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
                                   int pad) {
   TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
   auto gyc = gy.contiguous();
   auto xc = x.contiguous();
-  const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
-  const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
-  TORCH_CHECK(OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2,
+  const int Co = gy.size(1), Ci = x.size(1);
+  WinoBwdwArgs a = wino_bwdw_args(x.size(0), Ci, x.size(2), x.size(3), Co, pad,
+                                  "wino_bwdw_fused");
+  TORCH_CHECK(gy.size(2) == a.OH && gy.size(3) == a.OW,
               "wino_bwdw_fused geometry");
-  TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0 && Co % 32 == 0 && Ci % 32 == 0,
-              "wino_bwdw_fused shape requirements");
-  const int tH = OH / 2, tW = OW / 2;
-  const int T = B * tH * tW;
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
-  const WinoSplit sp = wino_bwdw_split(Co, Ci, T);
-  const int splits = sp.splits;
-
-  auto slab = at::empty({splits, Co, Ci, 3, 3}, x.options());
-  FastDiv d_thw, d_tw;
-  d_thw.init(tH * tW);
-  d_tw.init(tW);
-  dim3 grid(Co / 32, Ci / 32, splits);
-  hipLaunchKernelGGL(wino_bwdw_fused_kernel, grid, dim3(256), 0, stream,
-                     gyc.data_ptr<float>(), xc.data_ptr<float>(),
-                     slab.data_ptr<float>(), B, Ci, H, W, Co, OH, OW, tH, tW,
-                     pad, sp.per, d_thw, d_tw);
-  if (splits == 1) {
+  auto slab = at::empty({a.nz, Co, Ci, 3, 3}, x.options());
+  a.gy = gyc.data_ptr<float>();
+  a.x = xc.data_ptr<float>();
+  a.slab = slab.data_ptr<float>();
+  hipLaunchKernelGGL(wino_bwdw_fused_kernel, dim3(a.nx, a.ny, a.nz), dim3(256),
+                     0, stream, a);
+  if (a.nz == 1) {
     return slab.view({Co, Ci, 3, 3});
   }
   auto gw = at::empty({Co, Ci, 3, 3}, x.options());
-  slab_reduce(slab.data_ptr<float>(), splits, gw.data_ptr<float>(), gw.numel(),
+  slab_reduce(slab.data_ptr<float>(), a.nz, gw.data_ptr<float>(), gw.numel(),
               stream);
   return gw;
 }
@@ -1013,47 +890,31 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, "wino_fused: 3x3 only");
   auto xc = x.contiguous();
   auto wc = w.contiguous();
-  const int B = x.size(0), H = x.size(2), W = x.size(3);
+  const int B = x.size(0);
   const int Co = flip ? w.size(1) : w.size(0);
   const int Ci = flip ? w.size(0) : w.size(1);
   TORCH_CHECK(x.size(1) == Ci, "wino_fused: channel mismatch");
-  const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
-  const int tH = OH / 2, tW = OW / 2;
-  const int T = B * tH * tW;
-  TORCH_CHECK(Co % 32 == 0 && T % 32 == 0 && Ci % 8 == 0 && OH % 2 == 0
-              && OW % 2 == 0, "wino_fused shape requirements");
-  auto stream = c10::hip::getCurrentHIPStream().stream();
   // the weight transform runs IN-KERNEL (one (co,ci) pair per thread per
   // staging step) — no wt launch, no 16*Co*Ci frequency tensor
-  const int CW = (int)w.size(1);
-  const WinoSplit sp = wino_fused_split(Co, Ci, T);
-  const int splits = sp.splits, ci_per = sp.per;
+  WinoFusedArgs a = wino_fused_args(B, Ci, x.size(2), x.size(3), Co, pad,
+                                    (int)w.size(1), "wino_fused");
+  auto stream = c10::hip::getCurrentHIPStream().stream();
 
   // every slice covers a non-empty ci range and T, Co are tile multiples, so
   // each slab is written in full
-  auto y = at::empty({B, Co, OH, OW}, x.options());
+  auto y = at::empty({B, Co, a.OH, a.OW}, x.options());
   at::Tensor slab;
-  if (splits > 1) slab = at::empty({splits, B, Co, OH, OW}, x.options());
-  float* yw = splits > 1 ? slab.data_ptr<float>() : y.data_ptr<float>();
-  FastDiv d_thw, d_tw;
-  d_thw.init(tH * tW);
-  d_tw.init(tW);
-  dim3 grid(T / 32, Co / 32, splits);
-  if (flip) {
-    hipLaunchKernelGGL(wino_fused_kernel<true>, grid, dim3(256), 0, stream,
-                       xc.data_ptr<float>(), wc.data_ptr<float>(),
-                       bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                       yw, B, Ci, H, W, Co, OH, OW, tH, tW,
-                       pad, ci_per, CW, d_thw, d_tw);
-  } else {
-    hipLaunchKernelGGL(wino_fused_kernel<false>, grid, dim3(256), 0, stream,
-                       xc.data_ptr<float>(), wc.data_ptr<float>(),
-                       bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                       yw, B, Ci, H, W, Co, OH, OW, tH, tW,
-                       pad, ci_per, CW, d_thw, d_tw);
-  }
-  if (splits > 1) {
-    slab_reduce(slab.data_ptr<float>(), splits, y.data_ptr<float>(), y.numel(),
+  if (a.nz > 1) slab = at::empty({a.nz, B, Co, a.OH, a.OW}, x.options());
+  a.x = xc.data_ptr<float>();
+  a.w = wc.data_ptr<float>();
+  a.bias = bias.has_value() ? bias->data_ptr<float>() : nullptr;
+  a.y = a.nz > 1 ? slab.data_ptr<float>() : y.data_ptr<float>();
+  wino_dispatch_flip(flip, [&](auto F) {
+    hipLaunchKernelGGL(wino_fused_kernel<decltype(F)::value>,
+                       dim3(a.nx, a.ny, a.nz), dim3(256), 0, stream, a);
+  });
+  if (a.nz > 1) {
+    slab_reduce(slab.data_ptr<float>(), a.nz, y.data_ptr<float>(), y.numel(),
                 stream);
   }
   return y;
@@ -1064,10 +925,10 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
 // conv2d_wino_fused(flip) and conv2d_wino_bwdw_fused use, alone or paired
 std::tuple<int, int, int, int> conv2d_bwd_pair_splits(int B, int Ci, int H,
                                                       int W, int Co, int pad) {
-  const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
-  const WinoSplit ds = wino_fused_split(Ci, Co, B * (H / 2) * (W / 2));
-  const WinoSplit ws = wino_bwdw_split(Co, Ci, B * (OH / 2) * (OW / 2));
-  return {ds.splits, ds.per, ws.splits, ws.per};
+  const WinoFusedArgs d = wino_bwd_data_args(B, Ci, H, W, Co, pad,
+                                             "bwd_pair_splits");
+  const WinoBwdwArgs g = wino_bwdw_args(B, Ci, H, W, Co, pad, "bwd_pair_splits");
+  return {d.nz, d.ci_per, g.nz, g.t_per};
 }
 
 // gx and gw of a 3x3 stride-1 layer from one wino_bwd_pair_kernel launch
@@ -1090,54 +951,34 @@ std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor& gy,
   TORCH_CHECK(gy.size(0) == B && w.size(0) == Co && w.size(1) == Ci &&
               OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2 && pad <= 2,
               "bwd_pair geometry");
-  // bwd-data: a fused conv of gy (Co channels, OH x OW) into Ci channels at
-  // H x W with pad 2 - pad; bwd-weight: tiles of gy
-  const int dtH = H / 2, dtW = W / 2, dT = B * dtH * dtW;
-  const int wtH = OH / 2, wtW = OW / 2, wT = B * wtH * wtW;
-  TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && OH % 2 == 0 && OW % 2 == 0 &&
-              Ci % 32 == 0 && Co % 32 == 0 && dT % 32 == 0,
-              "bwd_pair shape requirements");
+  WinoFusedArgs d = wino_bwd_data_args(B, Ci, H, W, Co, pad, "bwd_pair");
+  WinoBwdwArgs g = wino_bwdw_args(B, Ci, H, W, Co, pad, "bwd_pair");
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const WinoSplit ds = wino_fused_split(Ci, Co, dT);
-  const WinoSplit ws = wino_bwdw_split(Co, Ci, wT);
 
   auto gx = at::empty({B, Ci, H, W}, x.options());
   at::Tensor gx_slab;
-  if (ds.splits > 1) gx_slab = at::empty({ds.splits, B, Ci, H, W}, x.options());
-  auto gw_slab = at::empty({ws.splits, Co, Ci, 3, 3}, x.options());
+  if (d.nz > 1) gx_slab = at::empty({d.nz, B, Ci, H, W}, x.options());
+  auto gw_slab = at::empty({g.nz, Co, Ci, 3, 3}, x.options());
 
-  WinoPairData d;
   d.x = gyc.data_ptr<float>();
   d.w = wc.data_ptr<float>();
-  d.y = ds.splits > 1 ? gx_slab.data_ptr<float>() : gx.data_ptr<float>();
-  d.B = B; d.Ci = Co; d.H = OH; d.W = OW; d.Co = Ci; d.OH = H; d.OW = W;
-  d.tH = dtH; d.tW = dtW; d.pad = 2 - pad; d.ci_per = ds.per; d.CW = Ci;
-  d.d_thw.init(dtH * dtW);
-  d.d_tw.init(dtW);
-  d.gx = dT / 32; d.gy = Ci / 32; d.n = d.gx * d.gy * ds.splits;
-  WinoPairWeight g;
+  d.y = d.nz > 1 ? gx_slab.data_ptr<float>() : gx.data_ptr<float>();
   g.gy = gyc.data_ptr<float>();
   g.x = xc.data_ptr<float>();
   g.slab = gw_slab.data_ptr<float>();
-  g.B = B; g.Ci = Ci; g.H = H; g.W = W; g.Co = Co; g.OH = OH; g.OW = OW;
-  g.tH = wtH; g.tW = wtW; g.pad = pad; g.t_per = ws.per;
-  g.d_thw.init(wtH * wtW);
-  g.d_tw.init(wtW);
-  g.gx = Co / 32; g.gy_ = Ci / 32; g.n = g.gx * g.gy_ * ws.splits;
   if (interleave < 0) interleave = WINO_PAIR_INTERLEAVE;
-  hipLaunchKernelGGL(wino_bwd_pair_kernel, dim3(d.n + g.n), dim3(256), 0,
-                     stream, d, g, interleave);
+  hipLaunchKernelGGL(wino_bwd_pair_kernel,
+                     dim3(d.nx * d.ny * d.nz + g.nx * g.ny * g.nz), dim3(256),
+                     0, stream, d, g, interleave);
 
-  at::Tensor gw = ws.splits > 1 ? at::empty({Co, Ci, 3, 3}, x.options())
-                                : gw_slab.view({Co, Ci, 3, 3});
-  if (ds.splits > 1 || ws.splits > 1) {
+  at::Tensor gw = g.nz > 1 ? at::empty({Co, Ci, 3, 3}, x.options())
+                           : gw_slab.view({Co, Ci, 3, 3});
+  if (d.nz > 1 || g.nz > 1) {
     // a side with one slice was written in place: no job for it
-    slab_reduce_pair(ds.splits > 1 ? gx_slab.data_ptr<float>() : nullptr,
-                     ds.splits, gx.data_ptr<float>(),
-                     ds.splits > 1 ? gx.numel() : 0,
-                     ws.splits > 1 ? gw_slab.data_ptr<float>() : nullptr,
-                     ws.splits, gw.data_ptr<float>(),
-                     ws.splits > 1 ? gw.numel() : 0, stream);
+    slab_reduce_pair(d.nz > 1 ? gx_slab.data_ptr<float>() : nullptr, d.nz,
+                     gx.data_ptr<float>(), d.nz > 1 ? gx.numel() : 0,
+                     g.nz > 1 ? gw_slab.data_ptr<float>() : nullptr, g.nz,
+                     gw.data_ptr<float>(), g.nz > 1 ? gw.numel() : 0, stream);
   }
   return {gx, gw};
 }

@@ -4,7 +4,14 @@ tile grids, paddings, K tails and slab counts at their smallest instances,
 against torch (atol = rtol = 1e-4, as test_conv2d_winograd) and bit-for-bit
 against the outputs the five-launch pipeline produced
 (tests/golden/wino_pipe_parent, written by tools/record_wino_pipe_golden.py
-on the parent commit)."""
+on the parent commit).
+
+Second family: conv2d_wino_bwdw, the unfused bwd-weight pipeline, against
+torch's conv weight gradient (atol = rtol = 2e-4, as test_bwdw_matches_torch
+of test_wino_fused_lds_gpu.py; the recording commit passes it at all five
+cases, worst error 0.2 of the bound at the stem shape) and bit-for-bit
+against the outputs recorded before its transform kernels moved onto the
+shared definitions of csrc/wino_math.h (two recordings held equal arrays)."""
 
 import functools
 import os
@@ -94,6 +101,61 @@ def test_bit_identical_to_parent(case, flip):
         if key in g.files:
             assert np.array_equal(g[key], a)
     got = y.cpu().numpy().reshape(-1)
+    if "idx" in g.files:
+        got = got[g["idx"]]
+    want = g["out"].reshape(-1)
+    assert np.array_equal(got, want), (
+        f"{name}: {np.count_nonzero(got != want)} of {got.size} elements "
+        f"differ from the parent's output")
+
+
+# ---- conv2d_wino_bwdw: gy transform, input transform, frequency GEMM over
+# the tile axis (matmul_f32's fixed-order split-K), gw transform.  The route
+# of the layers whose channel counts are no multiples of 32.
+# (B, Ci, H, W, Co, pad)
+BWDW_CASES = [
+    (2, 8, 4, 4, 16, 1),       # T = 8, one K-step, every patch touches padding
+    (3, 24, 6, 10, 40, 1),     # non-square tiles, T = 45 (K tail), channels not multiples of 32
+    (2, 8, 10, 10, 24, 0),     # pad 0: no tap masked
+    (2, 8, 6, 6, 16, 2),       # pad 2
+    (4, 3, 32, 32, 64, 1),     # the stem: T = 1024, the GEMM's K splits and its slab reduce runs
+]
+BWDW_TOL = dict(atol=2e-4, rtol=2e-4)   # as test_bwdw_matches_torch
+
+
+def test_bwdw_case_table_matches_recorder():
+    assert BWDW_CASES == rec.BWDW_CASES
+
+
+@functools.lru_cache(maxsize=None)
+def _run_bwdw(case):
+    from split_learning_amd.ops.functional import native
+    gy, x = rec.bwdw_inputs(case)
+    return (gy, x), native().conv2d_wino_bwdw(_dev(gy), _dev(x), case[5])
+
+
+@pytest.mark.parametrize("case", BWDW_CASES, ids=_ids)
+def test_bwdw_matches_torch(case):
+    B, Ci, H, W, Co, pad = case
+    (gy, x), gw = _run_bwdw(case)
+    wr = torch.zeros(Co, Ci, 3, 3, device="cuda", requires_grad=True)
+    F.conv2d(_dev(x), wr, None, 1, pad).backward(_dev(gy))
+    print(f"bwdw {_ids(case)}: max |gw - torch| = "
+          f"{float((gw - wr.grad).abs().max()):.3e}, "
+          f"max |torch| = {float(wr.grad.abs().max()):.3e}")
+    torch.testing.assert_close(gw, wr.grad, **BWDW_TOL)
+
+
+@pytest.mark.parametrize("case", BWDW_CASES, ids=_ids)
+def test_bwdw_bit_identical_to_parent(case):
+    inputs, gw = _run_bwdw(case)
+    name = rec.bwdw_name(case)
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    assert str(g["sha256"]) == rec.digest(inputs), "inputs differ from the recorded ones"
+    for key, a in zip(("gy", "x"), inputs):
+        if key in g.files:
+            assert np.array_equal(g[key], a)
+    got = gw.cpu().numpy().reshape(-1)
     if "idx" in g.files:
         got = got[g["idx"]]
     want = g["out"].reshape(-1)

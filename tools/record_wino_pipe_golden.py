@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Record conv2d_wino's outputs as bit-exact fixtures (run on the GPU box, at
-the commit whose results are the reference).
+"""Record conv2d_wino's and conv2d_wino_bwdw's outputs as bit-exact fixtures
+(run on the GPU box, at the commit whose results are the reference).
 
   python tools/record_wino_pipe_golden.py [out_dir]   # default tests/golden/wino_pipe_parent
 
-One .npz per case and direction of tests/test_wino_pipe_gpu.py.  Inputs come
+One .npz per case (and direction) of tests/test_wino_pipe_gpu.py; a file that
+already exists is left as it is, so only new cases are written.  Inputs come
 from numpy's frozen RandomState stream of the case's seed, weights scaled by
 0.1; their sha256 is stored, and the arrays themselves when they are small.  An
 output above 64 K elements is stored as a fixed seeded 64 K-element sample
@@ -32,6 +33,14 @@ PIPE_CASES = [
     (2, 96, 8, 8, 64, 1),
     (4, 256, 2, 2, 256, 1),
 ]
+# conv2d_wino_bwdw cases (B, Ci, H, W, Co, pad)
+BWDW_CASES = [
+    (2, 8, 4, 4, 16, 1),
+    (3, 24, 6, 10, 40, 1),
+    (2, 8, 10, 10, 24, 0),
+    (2, 8, 6, 6, 16, 2),
+    (4, 3, 32, 32, 64, 1),
+]
 
 SAMPLE = 65536          # output elements kept of a large output
 STORE_INPUTS = 8192   # inputs are stored up to this many elements in all
@@ -40,6 +49,11 @@ STORE_INPUTS = 8192   # inputs are stored up to this many elements in all
 def pipe_name(case, flip):
     B, Ci, H, W, Co, pad = case
     return f"pipe_b{B}_ci{Ci}_{H}x{W}_co{Co}_p{pad}_{'flip' if flip else 'fwd'}"
+
+
+def bwdw_name(case):
+    B, Ci, H, W, Co, pad = case
+    return f"bwdw_b{B}_ci{Ci}_{H}x{W}_co{Co}_p{pad}"
 
 
 def case_seed(name):
@@ -55,6 +69,15 @@ def pipe_inputs(case, flip):
     w = (rs.standard_normal(wshape) * 0.1).astype(np.float32)
     bias = None if flip else rs.standard_normal((Co,)).astype(np.float32)
     return x, w, bias
+
+
+def bwdw_inputs(case):
+    """gy [B,Co,OH,OW], x [B,Ci,H,W]."""
+    B, Ci, H, W, Co, pad = case
+    rs = np.random.RandomState(case_seed(bwdw_name(case)))
+    gy = rs.standard_normal((B, Co, H + 2 * pad - 2, W + 2 * pad - 2)).astype(np.float32)
+    x = rs.standard_normal((B, Ci, H, W)).astype(np.float32)
+    return gy, x
 
 
 def digest(arrays):
@@ -73,6 +96,10 @@ def sample_idx(name, numel):
 
 
 def save(out_dir, name, inputs, out):
+    path = os.path.join(out_dir, name + ".npz")
+    if os.path.exists(path):
+        print(f"{name}: exists, kept", flush=True)
+        return
     rec = {"sha256": np.array(digest(inputs.values()))}
     if sum(a.size for a in inputs.values() if a is not None) <= STORE_INPUTS:
         rec.update({k: v for k, v in inputs.items() if v is not None})
@@ -83,7 +110,7 @@ def save(out_dir, name, inputs, out):
     else:
         rec["idx"] = idx
         rec["out"] = flat[idx]
-    np.savez_compressed(os.path.join(out_dir, name + ".npz"), **rec)
+    np.savez_compressed(path, **rec)
     print(f"{name}: out {tuple(out.shape)}"
           + (f" sampled {SAMPLE}" if idx is not None else ""), flush=True)
 
@@ -106,6 +133,10 @@ def main():
             y = n.conv2d_wino(t(x), t(w), t(bias), case[5], flip)
             save(out_dir, pipe_name(case, flip),
                  {"x": x, "w": w, "bias": bias}, y.cpu().numpy())
+    for case in BWDW_CASES:
+        gy, x = bwdw_inputs(case)
+        gw = n.conv2d_wino_bwdw(t(gy), t(x), case[5])
+        save(out_dir, bwdw_name(case), {"gy": gy, "x": x}, gw.cpu().numpy())
     torch.cuda.synchronize()
 
 

@@ -1,11 +1,9 @@
 #!/usr/bin/env python3
 """Time conv2d_wino, forward and bwd-data (flip), at the flagship step's three
-Wino-routed shapes (GPU box).  The pipeline form is whatever SLK_WINO_PIPE
-selects for the process (bit 0: weight and input transform in one launch,
-bit 1: slab sum in the output transform; default 3, 0 = five launches), so an
-A/B is one process per value:
+Wino-routed shapes (GPU box): the three-launch pipeline (weight and input
+transform in one launch, the frequency GEMM, slab sum in the output transform).
 
-  for m in 0 1 2 3; do SLK_WINO_PIPE=$m python tools/wino_pipe_bench.py; done
+  python tools/wino_pipe_bench.py
 
 Each figure is us per call from a captured graph of CALLS back-to-back calls
 (as the benchmark replays them: no launch overhead between kernels), best and
@@ -56,7 +54,6 @@ def graph_us(fn):
 
 def main():
     n = native()
-    mode = os.environ.get("SLK_WINO_PIPE", "3")
     torch.manual_seed(3)
     for (B, C, H, W) in SHAPES:
         x = torch.randn(B, C, H, W, device="cuda")
@@ -64,7 +61,7 @@ def main():
         bias = torch.randn(C, device="cuda")
         fb, fm = graph_us(lambda: n.conv2d_wino(x, w, bias, 1, False))
         bb, bm = graph_us(lambda: n.conv2d_wino(x, w, None, 1, True))
-        print(f"pipe {mode} {B}x{C}x{H}x{W}: fwd best {fb:6.1f} med {fm:6.1f}"
+        print(f"pipe {B}x{C}x{H}x{W}: fwd best {fb:6.1f} med {fm:6.1f}"
               f"  flip best {bb:6.1f} med {bm:6.1f} us/call", flush=True)
 
 
