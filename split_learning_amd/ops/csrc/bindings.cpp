@@ -99,10 +99,12 @@ void adamw_step(std::vector<at::Tensor>, std::vector<at::Tensor>,
                 double, double, double, double, bool);
 at::Tensor make_opt_desc(std::vector<at::Tensor>, std::vector<at::Tensor>,
                          std::vector<at::Tensor>, std::vector<at::Tensor>);
+void grad_norm_fused(const at::Tensor&, int64_t, int64_t, double, const at::Tensor&,
+                     const at::Tensor&);
 void sgd_step_fused(const at::Tensor&, int64_t, int64_t, double, double, double,
-                    bool, bool);
+                    bool, bool, c10::optional<at::Tensor>);
 void adamw_step_fused(const at::Tensor&, int64_t, int64_t, int64_t, double, double,
-                      double, double, double, bool);
+                      double, double, double, bool, c10::optional<at::Tensor>);
 }  // namespace slk
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -191,6 +193,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_step", &slk::sgd_step);
   m.def("adamw_step", &slk::adamw_step);
   m.def("make_opt_desc", &slk::make_opt_desc);
-  m.def("sgd_step_fused", &slk::sgd_step_fused);
-  m.def("adamw_step_fused", &slk::adamw_step_fused);
+  m.def("grad_norm_fused", &slk::grad_norm_fused, py::arg("desc"), py::arg("n"),
+        py::arg("chunks"), py::arg("max_norm"), py::arg("partial"),
+        py::arg("out"));
+  m.def("sgd_step_fused", &slk::sgd_step_fused, py::arg("desc"), py::arg("n"),
+        py::arg("chunks"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("first"), py::arg("zero_after"),
+        py::arg("grad_scale") = py::none());
+  m.def("adamw_step_fused", &slk::adamw_step_fused, py::arg("desc"), py::arg("n"),
+        py::arg("chunks"), py::arg("step"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("zero_after"), py::arg("grad_scale") = py::none());
 }

@@ -205,6 +205,9 @@ class ClientRuntime:
 
     def _handle_syn(self, max_batches=None, on_step=None):
         sch = self.scheduler_cfg
+        debug_last = (self.logger is not None
+                      and getattr(self.logger, "debug_mode", False)
+                      and self.layer_id == self.n_stages)
         ctx = StageContext(
             client_id=self.client_id, layer_id=self.layer_id,
             n_stages=self.n_stages, cluster=self.cluster, model=self.model,
@@ -223,8 +226,11 @@ class ClientRuntime:
             # we keep that behind debug_mode since .item() syncs the device
             log_loss=((lambda loss: self.logger.log_debug(
                 f"client {self.client_id} loss: {float(loss.detach()):.6f}"))
-                if (self.logger is not None and getattr(self.logger, "debug_mode", False)
-                    and self.layer_id == self.n_stages) else None),
+                if debug_last else None),
+            # the pre-clip gradient norm of each clipped step, same debug gate
+            log_grad_norm=((lambda norm: self.logger.log_debug(
+                f"client {self.client_id} grad norm: {float(norm):.6f}"))
+                if debug_last else None),
         )
         result, size = run_stage(ctx)
         pause_msg = ctx.pause_msg

@@ -7,10 +7,9 @@ AdamW(lr, weight_decay) for BERT/KWT (src/train/BERT.py:69, KWT.py:62).
 
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
-
 
 
 SLK_OPT_CHUNK = 16384
@@ -76,16 +75,61 @@ def _host_for_build(opt) -> torch.Tensor:
     return opt._host
 
 
+def _clip_on(opt) -> bool:
+    """max_grad_norm None or <= 0 means off (reference: `if clip_grad_norm
+    and clip_grad_norm > 0`, other/Vanilla_SL/src/Scheduler.py:204)."""
+    return opt.max_grad_norm is not None and opt.max_grad_norm > 0
+
+
+def _clip_buffers(opt, chunks: int, device):
+    """Buffers of the native gradient-norm clip, allocated with the
+    descriptor and cached with it (a build inside hipGraph capture takes them
+    from the capture pool): per-chunk float64 sums of squares, the float32
+    [norm, coef] pair the fused step reads, and the norm as a view of it."""
+    if not _clip_on(opt):
+        return None
+    partial = torch.empty(chunks, dtype=torch.float64, device=device)
+    out = torch.empty(2, dtype=torch.float32, device=device)
+    return partial, out, out[0]
+
+
+def _grad_scale(opt, desc, n, chunks, clip):
+    """Launch the norm + coefficient kernels over the step's descriptor and
+    return the tensor the fused step scales by (None = clipping off).  No
+    host sync: last_grad_norm stays a device scalar."""
+    if clip is None:
+        return None
+    from ..ops import native
+    partial, out, norm = clip
+    native().grad_norm_fused(desc, n, chunks, float(opt.max_grad_norm), partial, out)
+    opt.last_grad_norm = norm
+    return out
+
+
+def _clip_cpu(opt, params):
+    """CPU tensors: torch's own clip on the live parameters' grads."""
+    if _clip_on(opt):
+        opt.last_grad_norm = torch.nn.utils.clip_grad_norm_(params, opt.max_grad_norm)
+
+
 class FusedSGD:
     def __init__(self, params, lr: float, momentum: float = 0.0,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None):
         self.params: List[torch.Tensor] = [p for p in params if p.requires_grad]
         self.lr = lr
         self.momentum = momentum
         self.weight_decay = weight_decay
+        # clip the total gradient 2-norm to this inside step() (torch's
+        # clip_grad_norm_ semantics, natively on the GPU); None or <= 0 = off.
+        # last_grad_norm: pre-clip norm of the last clipped step, a device
+        # scalar that step() never syncs; None before the first clipped step.
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.bufs = [torch.zeros_like(p) for p in self.params]
         self.steps = 0
-        self._desc_cache = None  # (ptr_signature, desc_tensor, n, chunks)
+        # (ptr_signature, desc_tensor, n, chunks, clip buffers or None)
+        self._desc_cache = None
         self._host = _pinned_host(len(self.params))
         # release_grads=True (default): drop p.grad after the fused step so the
         # next backward MOVES fresh gradients in (AccumulateGrad steals the
@@ -101,15 +145,16 @@ class FusedSGD:
         release_grads the allocator usually hands the same blocks back, so
         the signature (and the table) is stable across eager steps."""
         sig = tuple(p.grad.data_ptr() for p, _ in live) + \
-              tuple(p.data_ptr() for p, _ in live)
+              tuple(p.data_ptr() for p, _ in live) + (_clip_on(self),)
         if self._desc_cache is None or self._desc_cache[0] != sig:
             params = [p for p, _ in live]
             bufs = [b for _, b in live]
             desc, chunks = _build_desc(_host_for_build(self), params,
                                        [p.grad for p, _ in live], bufs, bufs,
                                        params[0].device)
-            self._desc_cache = (sig, desc, len(params), chunks)
-        return self._desc_cache[1], self._desc_cache[2], self._desc_cache[3]
+            self._desc_cache = (sig, desc, len(params), chunks,
+                                _clip_buffers(self, chunks, params[0].device))
+        return self._desc_cache[1:]
 
     def zero_grad(self):
         """No-op by design: step() zeroes grads in the update kernel itself
@@ -122,11 +167,12 @@ class FusedSGD:
         if not live:
             return
         if live[0][0].is_cuda:
-            desc, n, chunks = self._desc(live)
+            desc, n, chunks, clip = self._desc(live)
             from ..ops import native
             native().sgd_step_fused(desc, n, chunks, self.lr, self.momentum,
                                     self.weight_decay, self.steps == 0,
-                                    not self.release_grads)
+                                    not self.release_grads,
+                                    _grad_scale(self, desc, n, chunks, clip))
             if self.release_grads:
                 # next backward MOVES fresh gradients in (no accumulate-add
                 # kernel per tensor); the allocator usually hands back the same
@@ -134,6 +180,7 @@ class FusedSGD:
                 for p, _ in live:
                     p.grad = None
         else:
+            _clip_cpu(self, [p for p, _ in live])
             for p, buf in live:
                 g = p.grad
                 if self.weight_decay:
@@ -151,12 +198,15 @@ class FusedSGD:
 
 class FusedAdamW:
     def __init__(self, params, lr: float, weight_decay: float = 0.01,
-                 betas=(0.9, 0.999), eps: float = 1e-8):
+                 betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: Optional[float] = None):
         self.params = [p for p in params if p.requires_grad]
         self.lr = lr
         self.weight_decay = weight_decay
         self.beta1, self.beta2 = betas
         self.eps = eps
+        self.max_grad_norm = max_grad_norm  # see FusedSGD
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
         self.steps = 0
@@ -166,7 +216,7 @@ class FusedAdamW:
 
     def _desc(self, live):
         sig = tuple(p.grad.data_ptr() for p, _, _ in live) + \
-              tuple(p.data_ptr() for p, _, _ in live)
+              tuple(p.data_ptr() for p, _, _ in live) + (_clip_on(self),)
         if self._desc_cache is None or self._desc_cache[0] != sig:
             params = [p for p, _, _ in live]
             desc, chunks = _build_desc(_host_for_build(self), params,
@@ -174,8 +224,9 @@ class FusedAdamW:
                                        [m for _, m, _ in live],
                                        [v for _, _, v in live],
                                        params[0].device)
-            self._desc_cache = (sig, desc, len(params), chunks)
-        return self._desc_cache[1], self._desc_cache[2], self._desc_cache[3]
+            self._desc_cache = (sig, desc, len(params), chunks,
+                                _clip_buffers(self, chunks, params[0].device))
+        return self._desc_cache[1:]
 
     def zero_grad(self):
         """No-op: see FusedSGD.zero_grad."""
@@ -188,11 +239,12 @@ class FusedAdamW:
         if not live:
             return
         if live[0][0].is_cuda:
-            desc, n, chunks = self._desc(live)
+            desc, n, chunks, clip = self._desc(live)
             from ..ops import native
             native().adamw_step_fused(desc, n, chunks, self.steps, self.lr,
                                       self.beta1, self.beta2, self.eps,
-                                      self.weight_decay, not self.release_grads)
+                                      self.weight_decay, not self.release_grads,
+                                      _grad_scale(self, desc, n, chunks, clip))
             if self.release_grads:
                 for p, _, _ in live:
                     p.grad = None
@@ -200,6 +252,7 @@ class FusedAdamW:
             b1, b2 = self.beta1, self.beta2
             bc1 = 1 - b1 ** self.steps
             bc2 = 1 - b2 ** self.steps
+            _clip_cpu(self, [p for p, _, _ in live])
             for p, m, v in live:
                 p.mul_(1 - self.lr * self.weight_decay)
                 m.mul_(b1).add_(p.grad, alpha=1 - b1)

@@ -131,6 +131,7 @@ class StageContext:
     sda_size: int = 1               # DCSL SDA batching at the last stage
     on_step: Any = None             # callback(step_idx) for benchmarking hooks
     log_loss: Any = None            # callback(loss_tensor) optional
+    log_grad_norm: Any = None       # callback(pre-clip norm tensor), debug only
     pause_msg: Optional[dict] = None  # PAUSE message that ended the stage loop
     stall_timeout_s: float = 120.0  # no-progress bound while work outstanding
 
@@ -234,6 +235,16 @@ def train_last_stage(ctx: StageContext):
     nan_flag = torch.zeros((), dtype=torch.bool, device=ctx.device)
     model.train()
     group: list = []
+    # Gradient-norm clipping happens on the last stage only, as in the
+    # reference (other/Vanilla_SL/src/Scheduler.py:204), and inside the
+    # optimizer's step: on the GPU a native norm pass whose coefficient the
+    # fused update applies as it loads each gradient.
+    clip = bool(ctx.clip_grad_norm and ctx.clip_grad_norm > 0)
+    if clip and not hasattr(opt, "max_grad_norm"):
+        raise TypeError(f"clip-grad-norm needs an optimizer that clips in step() "
+                        f"(FusedSGD / FusedAdamW), not {type(opt).__name__}")
+    if hasattr(opt, "max_grad_norm"):
+        opt.max_grad_norm = ctx.clip_grad_norm if clip else None
 
     def process(batch_msgs):
         nonlocal data_count
@@ -249,11 +260,9 @@ def train_last_stage(ctx: StageContext):
         if ctx.log_loss is not None:
             ctx.log_loss(loss)
         loss.backward()
-        if ctx.clip_grad_norm:
-            torch.nn.utils.clip_grad_norm_(
-                [p for p in model.parameters() if p.grad is not None],
-                ctx.clip_grad_norm)
-        opt.step()
+        opt.step()   # clips first when max_grad_norm is set (see above)
+        if ctx.log_grad_norm is not None and clip:
+            ctx.log_grad_norm(opt.last_grad_norm)
         data_count += act.shape[0]
         off = 0
         for m in batch_msgs:
