@@ -56,6 +56,9 @@ def _flags():
     ] + [f"-I{p}" for p in includes]
     if os.environ.get("SLK_MFMA32"):  # 32x32x2 MFMA core variant (A/B experiments)
         cxxflags.append("-DSLK_MFMA32")
+    for knob in ("SLK_BN_U", "SLK_SLAB_U"):  # batch-depth sweeps (common.h)
+        if os.environ.get(knob):
+            cxxflags.append(f"-D{knob}={int(os.environ[knob])}")
     ldflags = [
         "-shared",
         f"-L{torch_lib}", "-ltorch", "-ltorch_cpu", "-ltorch_python", "-lc10",

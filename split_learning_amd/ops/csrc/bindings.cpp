@@ -7,6 +7,7 @@ at::Tensor matmul_f32(const at::Tensor&, const at::Tensor&, bool, bool,
                       c10::optional<at::Tensor>, bool);
 at::Tensor linear_fwd(const at::Tensor&, const at::Tensor&, c10::optional<at::Tensor>);
 at::Tensor colsum_f32(const at::Tensor&);
+int matmul_f32_slab_count(int, int, int, int);
 // wino.hip
 at::Tensor conv2d_wino(const at::Tensor&, const at::Tensor&,
                        c10::optional<at::Tensor>, int, bool);
@@ -114,6 +115,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none(), py::arg("accumulate") = false);
   m.def("linear_fwd", &slk::linear_fwd);
   m.def("colsum_f32", &slk::colsum_f32);
+  m.def("matmul_f32_slab_count", &slk::matmul_f32_slab_count, py::arg("nb"),
+        py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("conv2d_wino", &slk::conv2d_wino, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("pad") = 1,
         py::arg("flip") = false);

@@ -106,6 +106,76 @@ struct FastDiv {
   }
 };
 
+// A loop i = first, first + step, ... < hi whose iterations each load and then
+// use, run U iterations at a time: the loads of U consecutive iterations are
+// issued before the first use, so a wave has U (times the loads per
+// iteration) memory requests in flight where the plain loop has one and waits
+// a full round trip per iteration.  use() runs in ascending i on the same
+// thread as in the plain loop, so whatever it accumulates keeps its order and
+// its bits.  What is left after the last full batch runs as one batch each of
+// U/2, U/4, ... 1 iterations where that many remain: nothing past hi is
+// loaded or used, and no load sits under a predicate of its own (the compiler
+// pulls the first use into such a block, and with it the wait).
+template <int U, class T, class I, class Load, class Use>
+__device__ __forceinline__ void slk_batched(I first, I hi, I step, Load load,
+                                            Use use) {
+  static_assert(U >= 1 && (U & (U - 1)) == 0, "U: a power of two");
+  I i = first;
+  // hi - (U - 1) * step cannot overflow where i + (U - 1) * step could
+  for (; i < hi - (U - 1) * step; i += U * step) {
+    T v[U];
+    #pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = load(i + u * step);
+    #pragma unroll
+    for (int u = 0; u < U; ++u) use(i + u * step, v[u]);
+  }
+  if constexpr (U > 1) slk_batched<U / 2, T>(i, hi, step, load, use);
+}
+
+// batch depths (loads in flight per wave and stream) of the reduction loops;
+// ops/build.py passes SLK_BN_U / SLK_SLAB_U from the environment for sweeps
+// with tools/reduce_bench.py (profiles/SUMMARY.md round 8)
+#ifndef SLK_BN_U
+#define SLK_BN_U 8      // BatchNorm sums and the one-launch kernels' phase 2
+#endif
+#ifndef SLK_SLAB_U
+#define SLK_SLAB_U 8    // split-K slab sums
+#endif
+
+// out[i] = 0.f + slab[i] + slab[numel + i] + ... in slab order, the split-K
+// finalize of every slab producer (conv2d.hip, wino.hip, gemm_f32.hip).
+// V is float, or f32x4 where numel % 4 == 0 and both bases are 16-byte
+// aligned (numel then counts vectors); a vector add is four scalar adds, so
+// an element's sum does not depend on V or on the thread that forms it.
+// (block, nblocks): the launch's blocks that work on this slab set
+template <class V>
+__device__ __forceinline__ void slab_reduce_body(const V* __restrict__ slab,
+                                                 int splits,
+                                                 V* __restrict__ out,
+                                                 long numel, int block,
+                                                 int nblocks) {
+  const long stride = (long)nblocks * blockDim.x;
+  for (long i = (long)block * blockDim.x + threadIdx.x; i < numel;
+       i += stride) {
+    V s = V(0.f);
+    slk_batched<SLK_SLAB_U, V>(
+        0, splits, 1, [&](int k) { return slab[(long)k * numel + i]; },
+        [&](int, const V& v) { s += v; });
+    out[i] = s;
+  }
+}
+
+static inline bool slab_is_vec4(const void* slab, const void* out, long numel) {
+  return numel % 4 == 0 && (((uintptr_t)slab | (uintptr_t)out) & 15) == 0;
+}
+
+// blocks of 256 threads for one slab set: a thread per float4 or per float
+static inline int slab_reduce_grid(const void* slab, const void* out,
+                                   long numel) {
+  const long n = slab_is_vec4(slab, out, numel) ? numel / 4 : numel;
+  return (int)std::min<long>((n + 255) / 256, 4096);
+}
+
 // block-level reduction into lane 0 of wave 0 (sums `val` over blockDim.x
 // threads; blockDim.x must be a multiple of 64 and <= 1024)
 template <typename T>

@@ -303,24 +303,25 @@ struct AtomicStore {
 // out[i] = sum_s slab[s*numel + i]: replaces (zero + atomic accumulate) with
 // streaming slab writes + one reduction pass — at split 64 on a 65 KB output
 // the atomic path was 4M serialized RMWs.
-// (block, nblocks): the launch's blocks that work on this slab set
-__device__ __forceinline__ void slab_reduce_body(const float* __restrict__ slab,
-                                                 int splits,
-                                                 float* __restrict__ out,
-                                                 long numel, int block,
-                                                 int nblocks) {
-  const long stride = (long)nblocks * blockDim.x;
-  for (long i = (long)block * blockDim.x + threadIdx.x; i < numel;
-       i += stride) {
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += slab[(long)k * numel + i];
-    out[i] = s;
+// slab_reduce_body (common.h) forms each sum; a set whose length and bases
+// allow it is summed four elements per thread with 16-byte loads
+__device__ __forceinline__ void slab_reduce_set(const float* __restrict__ slab,
+                                                int splits,
+                                                float* __restrict__ out,
+                                                long numel, bool vec4, int block,
+                                                int nblocks) {
+  if (vec4) {
+    slab_reduce_body(reinterpret_cast<const f32x4*>(slab), splits,
+                     reinterpret_cast<f32x4*>(out), numel / 4, block, nblocks);
+  } else {
+    slab_reduce_body(slab, splits, out, numel, block, nblocks);
   }
 }
 
 __global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
-                                   float* __restrict__ out, long numel) {
-  slab_reduce_body(slab, splits, out, numel, blockIdx.x, gridDim.x);
+                                   float* __restrict__ out, long numel,
+                                   bool vec4) {
+  slab_reduce_set(slab, splits, out, numel, vec4, blockIdx.x, gridDim.x);
 }
 
 // two independent slab sets in one launch (the gx and gw slabs of a paired
@@ -328,38 +329,40 @@ __global__ void slab_reduce_kernel(const float* __restrict__ slab, int splits,
 // element as slab_reduce_kernel sums it
 __global__ void slab_reduce_pair_kernel(const float* __restrict__ slab_a,
                                         int splits_a, float* __restrict__ out_a,
-                                        long numel_a, int blocks_a,
+                                        long numel_a, bool vec4_a, int blocks_a,
                                         const float* __restrict__ slab_b,
                                         int splits_b, float* __restrict__ out_b,
-                                        long numel_b) {
+                                        long numel_b, bool vec4_b) {
   if ((int)blockIdx.x < blocks_a) {
-    slab_reduce_body(slab_a, splits_a, out_a, numel_a, blockIdx.x, blocks_a);
+    slab_reduce_set(slab_a, splits_a, out_a, numel_a, vec4_a, blockIdx.x,
+                    blocks_a);
   } else {
-    slab_reduce_body(slab_b, splits_b, out_b, numel_b, blockIdx.x - blocks_a,
-                     gridDim.x - blocks_a);
+    slab_reduce_set(slab_b, splits_b, out_b, numel_b, vec4_b,
+                    blockIdx.x - blocks_a, gridDim.x - blocks_a);
   }
 }
 
-static int slab_reduce_grid(long numel) {
-  return (int)std::min<long>((numel + 255) / 256, 4096);
-}
-
-// shared with wino.hip's ci-/tile-split slabs (declared in torch_util.h)
+// shared with wino.hip's ci-/tile-split slabs and gemm_f32.hip's split-K
+// (declared in torch_util.h)
 void slab_reduce(const float* slab, int splits, float* out, long numel,
                  hipStream_t stream) {
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(slab_reduce_grid(numel)),
-                     dim3(256), 0, stream, slab, splits, out, numel);
+  hipLaunchKernelGGL(slab_reduce_kernel,
+                     dim3(slab_reduce_grid(slab, out, numel)), dim3(256), 0,
+                     stream, slab, splits, out, numel,
+                     slab_is_vec4(slab, out, numel));
 }
 
 void slab_reduce_pair(const float* slab_a, int splits_a, float* out_a,
                       long numel_a, const float* slab_b, int splits_b,
                       float* out_b, long numel_b, hipStream_t stream) {
-  const int blocks_a = slab_reduce_grid(numel_a);   // 0 for an empty set
-  const int blocks_b = slab_reduce_grid(numel_b);
+  const int blocks_a = slab_reduce_grid(slab_a, out_a, numel_a);   // 0 for an empty set
+  const int blocks_b = slab_reduce_grid(slab_b, out_b, numel_b);
   if (blocks_a + blocks_b == 0) return;
   hipLaunchKernelGGL(slab_reduce_pair_kernel, dim3(blocks_a + blocks_b),
                      dim3(256), 0, stream, slab_a, splits_a, out_a, numel_a,
-                     blocks_a, slab_b, splits_b, out_b, numel_b);
+                     slab_is_vec4(slab_a, out_a, numel_a), blocks_a, slab_b,
+                     splits_b, out_b, numel_b,
+                     slab_is_vec4(slab_b, out_b, numel_b));
 }
 
 // slab mode threshold: slab stores beat atomics once MANY splits pile on

@@ -57,19 +57,9 @@ struct StridedStore {
   }
 };
 
-// out[i] = sum_s slab[s*numel + i] in fixed order: split-K partial sums are
-// added the same way every run (atomic accumulation is order-dependent for
+// split-K partial sums are added by slab_reduce (conv2d.hip) in fixed slab
+// order, the same way every run (atomic accumulation is order-dependent for
 // three or more splits, and training amplifies that rounding noise)
-__global__ void gemm_slab_reduce_kernel(const float* __restrict__ slab, int splits,
-                                        float* __restrict__ out, long numel) {
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < numel;
-       i += stride) {
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += slab[(long)k * numel + i];
-    out[i] = s;
-  }
-}
 
 // split_k > 1: every split writes its own slab, reduced into c afterwards —
 // or, with keep_slabs, handed back unreduced as [splits * numel(c)] for a
@@ -114,9 +104,8 @@ static void launch_strided(const at::Tensor& a2, const at::Tensor& b2, at::Tenso
   if (split_k > 1 && keep_slabs != nullptr) {
     *keep_slabs = slab;
   } else if (split_k > 1) {
-    const int grid = (int)std::min<long>((numel + 255) / 256, 4096);
-    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3(grid), dim3(256), 0, stream,
-                       slab.data_ptr<float>(), split_k, c.data_ptr<float>(), numel);
+    slab_reduce(slab.data_ptr<float>(), split_k, c.data_ptr<float>(), numel,
+                stream);
   }
 }
 
@@ -163,7 +152,7 @@ int matmul_f32_slab_count(int nb, int M, int N, int K) {
 
 // Batched a @ b (3-D, no transposes) with matmul_f32's split-K choice, the
 // slabs left unreduced: returns [splits, nb, M, N], of which the caller adds
-// slab 0, 1, ... in order as gemm_slab_reduce_kernel would.  The Winograd
+// slab 0, 1, ... in order as slab_reduce would.  The Winograd
 // output transform takes its M this way (wino.hip).
 at::Tensor matmul_f32_slabs(const at::Tensor& a, const at::Tensor& b) {
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 3 && b.dim() == 3 &&

@@ -99,6 +99,31 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
   for (int row = blockIdx.x * waves + wid; row < B; row += gridDim.x * waves) {
     const float* xr = logits + (long)row * C;
     float* pr = probs + (long)row * C;
+    if (C <= 64) {
+      // a lane per class: logit and exp stay in registers, probs is written
+      // once (e * inv, the value the store-reload-multiply below leaves), and
+      // the label is fetched before the reductions; its logit comes from the
+      // lane that holds it
+      const bool in = lane < C;
+      const int64_t lbl = labels[row];
+      const float xv = in ? xr[lane] : 0.f;
+      float m = in ? fmaxf(-INFINITY, xv) : -INFINITY;
+      for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+      const float e = expf(xv - m);
+      float s = 0.f;
+      if (in) s += e;
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      const float inv = 1.f / s;
+      if (in) pr[lane] = e * inv;
+      // a label outside [0, C) is the caller's error here as in the loop form
+      // (there an out-of-bounds read, here another lane's value)
+      const float xl = __shfl(xv, (int)lbl, 64);
+      if (lane == 0) {
+        const float lse = m + logf(s);
+        acc += (lse - xl) / (float)B;
+      }
+      continue;
+    }
     float m = -INFINITY;
     for (int d = lane; d < C; d += 64) m = fmaxf(m, xr[d]);
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));

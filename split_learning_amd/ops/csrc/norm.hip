@@ -70,13 +70,83 @@ __device__ __forceinline__ float bn_relu_pool_window(const float* __restrict__ x
   return best;
 }
 
+// The 2x2 window of pooled output `rem` (= oh*OW + ow) of one (b, c) plane,
+// fetched ahead of its use: w is the window as a plane of row length 2, which
+// is how bn_relu_pool_window is then called on it; o is where the pooled
+// output goes.
+struct BnWindow {
+  float w[4];
+  long o;
+};
+
+__device__ __forceinline__ BnWindow bn_window_load(const float* __restrict__ plane,
+                                                   unsigned rem, long o,
+                                                   const PoolGeom& pg) {
+  const unsigned oh = pg.d_ow.div(rem);
+  const unsigned ow = pg.d_ow.mod(rem, oh);
+  const float* xp = plane + (long)(oh * 2) * pg.W + ow * 2;
+  return BnWindow{{xp[0], xp[1], xp[pg.W], xp[pg.W + 1]}, o};
+}
+
+// batch depth of the loop that fetches a window (four loads) per iteration
+constexpr int BN_POOL_U = 4;
+
 // Gradient arriving at full-resolution element (bc, r), r = h*W + w.
-// !POOL: gy/relu_y are full resolution; relu_y != nullptr fuses the ReLU
-// backward mask (g = y>0 ? gy : 0).  POOL: gy, relu_y (the pooled output) and
-// idx are at pooled resolution — the element gets the pooled gradient iff it
-// was the window's argmax and the pooled value passed the ReLU, which is what
+// !POOL: gy/relu_y are full resolution; RELU fuses the ReLU backward mask
+// (g = y>0 ? gy : 0).  POOL: gy, relu_y (the pooled output) and idx are at
+// pooled resolution — the element gets the pooled gradient iff it was the
+// window's argmax and the pooled value passed the ReLU, which is what
 // maxpool_bwd followed by the full-resolution mask yields.  The test is
 // !(y <= 0) so a NaN behaves as in the full-resolution mask.
+// Fetch and selection are apart so that a loop can issue the fetches of
+// several elements before the first selection (slk_batched): bn_gy_load reads
+// every operand unconditionally (all three addresses are valid for every
+// in-range element; a short-circuit here was up to three serial round trips
+// per element), bn_gy_select applies the predicates.
+struct BnGy {
+  float gy, ry;
+  uint8_t idx, pos;
+};
+
+template <bool POOL, bool RELU>
+__device__ __forceinline__ BnGy bn_gy_load(const float* __restrict__ gy,
+                                           const float* __restrict__ relu_y,
+                                           const uint8_t* __restrict__ idx,
+                                           long off, unsigned bc, unsigned r,
+                                           const PoolGeom& pg) {
+  BnGy v{};
+  if (POOL) {
+    const unsigned h = pg.d_w.div(r);
+    const unsigned w = pg.d_w.mod(r, h);
+    const long o = ((long)bc * pg.OH + (h >> 1)) * pg.OW + (w >> 1);
+    v.pos = (uint8_t)(((h & 1) << 1) | (w & 1));
+    v.idx = idx[o];
+    v.ry = relu_y[o];
+    v.gy = gy[o];
+  } else {
+    v.gy = gy[off];
+    if (RELU) v.ry = relu_y[off];
+  }
+  return v;
+}
+
+template <bool POOL, bool RELU>
+__device__ __forceinline__ float bn_gy_select(const BnGy& v) {
+  if (POOL) return (v.idx == v.pos && !(v.ry <= 0.f)) ? v.gy : 0.f;
+  if (RELU) return v.ry <= 0.f ? 0.f : v.gy;
+  return v.gy;
+}
+
+// relu_y == nullptr is uniform over the launch: one branch around a loop, not
+// one per element.  f(std::true_type / std::false_type) gets RELU.
+template <bool POOL, class F>
+__device__ __forceinline__ void bn_relu_dispatch(const float* relu_y, F&& f) {
+  if (POOL || relu_y != nullptr) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// The short-circuit form of load + select, one element at a time: what
+// bn_bwd_dx_kernel, which gained nothing from batching, still uses.
 template <bool POOL>
 __device__ __forceinline__ float bn_gy_at(const float* __restrict__ gy,
                                           const float* __restrict__ relu_y,
@@ -97,21 +167,27 @@ __device__ __forceinline__ float bn_gy_at(const float* __restrict__ gy,
 }
 
 // sum(x) and sum(x^2) of channel c over the linear (b, hw) range [lo, hi):
-// thread t accumulates lo+t, lo+t+blockDim, ... in double, then the block
-// sum.  Result valid in thread 0.
+// thread t accumulates lo+t, lo+t+blockDim, ... in double, one s and one s2
+// per thread, then the block sum.  Result valid in thread 0.
 __device__ __forceinline__ void bn_stat_sums(const float* __restrict__ x, int c,
                                              int lo, int hi, int C, int HW,
                                              const FastDiv& d_hw, double* scratch,
                                              double& ts, double& ts2) {
   double s = 0.0, s2 = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    // FastDiv: the plain i / HW was a ~25-VALU runtime division PER ELEMENT
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const double v = (double)x[((long)b * C + c) * HW + r];
-    s += v;
-    s2 += v * v;
-  }
+  slk_batched<SLK_BN_U, float>(
+      lo + (int)threadIdx.x, hi, (int)blockDim.x,
+      [&](int i) {
+        // FastDiv: the plain i / HW was a ~25-VALU runtime division PER ELEMENT
+        const unsigned b = d_hw.div((unsigned)i);
+        const unsigned r = d_hw.mod((unsigned)i, b);
+        return x[((long)b * C + c) * HW + r];
+      },
+      [&](int, float xv) {
+        // one add, one fma: what `s += v; s2 += v * v` has always compiled to
+        const double v = (double)xv;
+        s += v;
+        s2 = __builtin_fma(v, v, s2);
+      });
   ts = slk_block_sum(s, scratch);
   __syncthreads();
   ts2 = slk_block_sum(s2, scratch);
@@ -286,25 +362,33 @@ __global__ void bn_fwd_one_kernel(const float* __restrict__ x,
   if (POOL) {
     const int ohow = pg.OH * pg.OW;
     const int ptotal = B * ohow;
-    for (int j = threadIdx.x; j < ptotal; j += blockDim.x) {
-      const unsigned b = pg.d_ohow.div((unsigned)j);
-      const unsigned rem = pg.d_ohow.mod((unsigned)j, b);
-      const unsigned oh = pg.d_ow.div(rem);
-      const unsigned ow = pg.d_ow.mod(rem, oh);
-      const long bc = (long)b * C + c;
-      const float* xp = x + bc * HW + (long)(oh * 2) * pg.W + ow * 2;
-      int bi;
-      const float best = bn_relu_pool_window(xp, pg.W, m, is, g, bt, bi);
-      y[bc * ohow + rem] = best;
-      idx[bc * ohow + rem] = (uint8_t)bi;
-    }
+    slk_batched<BN_POOL_U, BnWindow>(
+        (int)threadIdx.x, ptotal, (int)blockDim.x,
+        [&](int j) {
+          const unsigned b = pg.d_ohow.div((unsigned)j);
+          const unsigned rem = pg.d_ohow.mod((unsigned)j, b);
+          const long bc = (long)b * C + c;
+          return bn_window_load(x + bc * HW, rem, bc * ohow + rem, pg);
+        },
+        [&](int, const BnWindow& v) {
+          int bi;
+          y[v.o] = bn_relu_pool_window(v.w, 2, m, is, g, bt, bi);
+          idx[v.o] = (uint8_t)bi;
+        });
   } else {
-    for (int i = threadIdx.x; i < total; i += blockDim.x) {
-      const unsigned b = d_hw.div((unsigned)i);
-      const unsigned r = d_hw.mod((unsigned)i, b);
-      const long off = ((long)b * C + c) * HW + r;
-      y[off] = bn_apply(x[off], m, is, g, bt, relu);
-    }
+    struct Elem {
+      float x;
+      long off;
+    };
+    slk_batched<SLK_BN_U, Elem>(
+        (int)threadIdx.x, total, (int)blockDim.x,
+        [&](int i) {
+          const unsigned b = d_hw.div((unsigned)i);
+          const unsigned r = d_hw.mod((unsigned)i, b);
+          const long off = ((long)b * C + c) * HW + r;
+          return Elem{x[off], off};
+        },
+        [&](int, const Elem& v) { y[v.off] = bn_apply(v.x, m, is, g, bt, relu); });
   }
 }
 
@@ -347,9 +431,32 @@ __global__ void bn_pool_fwd_kernel(const float* __restrict__ x,
   }
 }
 
+// x and the incoming gradient's operands of element i of channel c's linear
+// (b, hw) range, as the backward loops fetch them
+struct BnElem {
+  float x;
+  BnGy g;
+  long off;
+};
+
+template <bool POOL, bool RELU>
+__device__ __forceinline__ BnElem bn_elem_load(
+    const float* __restrict__ x, const float* __restrict__ gy,
+    const float* __restrict__ relu_y, const uint8_t* __restrict__ idx, int i,
+    int c, int C, int HW, const FastDiv& d_hw, const PoolGeom& pg) {
+  const unsigned b = d_hw.div((unsigned)i);
+  const unsigned r = d_hw.mod((unsigned)i, b);
+  const unsigned bc = b * (unsigned)C + c;
+  BnElem v;
+  v.off = (long)bc * HW + r;
+  v.x = x[v.off];
+  v.g = bn_gy_load<POOL, RELU>(gy, relu_y, idx, v.off, bc, r, pg);
+  return v;
+}
+
 // reductions for backward: sum(gy) and sum(gy * xhat) of channel c over the
 // linear (b, hw) range [lo, hi), same per-thread order as bn_stat_sums.
-// The incoming gradient is fetched through bn_gy_at, so the preceding ReLU's
+// The incoming gradient is fetched through bn_gy_load, so the preceding ReLU's
 // mask (and, POOL, the max-pool scatter) ride inside the reduction — no
 // standalone relu_bwd / maxpool_bwd launch, no extra full tensor pass.
 template <bool POOL>
@@ -359,15 +466,22 @@ __device__ __forceinline__ void bn_bwd_sums(
     float is, int c, int lo, int hi, int C, int HW, const FastDiv& d_hw,
     const PoolGeom& pg, double* scratch, double& ts, double& tsx) {
   double s = 0.0, sx = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const unsigned bc = b * (unsigned)C + c;
-    const long off = (long)bc * HW + r;
-    const double g = (double)bn_gy_at<POOL>(gy, relu_y, idx, off, bc, r, pg);
-    s += g;
-    sx += g * (double)((x[off] - m) * is);
-  }
+  bn_relu_dispatch<POOL>(relu_y, [&](auto R) {
+    constexpr bool RELU = decltype(R)::value;
+    slk_batched<SLK_BN_U, BnElem>(
+        lo + (int)threadIdx.x, hi, (int)blockDim.x,
+        [&](int i) {
+          return bn_elem_load<POOL, RELU>(x, gy, relu_y, idx, i, c, C, HW, d_hw,
+                                          pg);
+        },
+        [&](int, const BnElem& v) {
+          // float xhat, then one add and one fma in double: what
+          // `s += g; sx += g * (double)((x - m) * is)` has always compiled to
+          const double g = (double)bn_gy_select<POOL, RELU>(v.g);
+          s += g;
+          sx = __builtin_fma(g, (double)((v.x - m) * is), sx);
+        });
+  });
   ts = slk_block_sum(s, scratch);
   __syncthreads();
   tsx = slk_block_sum(sx, scratch);
@@ -452,14 +566,19 @@ __global__ void bn_bwd_one_kernel(const float* __restrict__ x,
   }
   __syncthreads();
   const float sgy = s_sum[0], sgx = s_sum[1], gm = gamma[c];
-  for (int i = threadIdx.x; i < total; i += blockDim.x) {
-    const unsigned b = d_hw.div((unsigned)i);
-    const unsigned r = d_hw.mod((unsigned)i, b);
-    const unsigned bc = b * (unsigned)C + c;
-    const long off = (long)bc * HW + r;
-    const float g = bn_gy_at<POOL>(gy, relu_y, idx, off, bc, r, pg);
-    gx[off] = bn_dx(x[off], g, m, is, gm, sgy, sgx, inv_n);
-  }
+  bn_relu_dispatch<POOL>(relu_y, [&](auto R) {
+    constexpr bool RELU = decltype(R)::value;
+    slk_batched<SLK_BN_U, BnElem>(
+        (int)threadIdx.x, total, (int)blockDim.x,
+        [&](int i) {
+          return bn_elem_load<POOL, RELU>(x, gy, relu_y, idx, i, c, C, HW, d_hw,
+                                          pg);
+        },
+        [&](int, const BnElem& v) {
+          gx[v.off] = bn_dx(v.x, bn_gy_select<POOL, RELU>(v.g), m, is, gm, sgy,
+                            sgx, inv_n);
+        });
+  });
 }
 
 __global__ void bn_bwd_finalize_kernel(const float* __restrict__ slab, int chunks,

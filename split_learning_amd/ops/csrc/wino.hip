@@ -144,7 +144,7 @@ __global__ void wino_wt_in_kernel(const float* __restrict__ w,
 // output transform y[b][co][2th..][2tw..] = A^T M A (+bias), with the
 // frequency GEMM's split-K sum folded in: M arrives as `splits` slabs
 // (slab_stride floats apart) and each element is summed here in
-// gemm_slab_reduce_kernel's order and form (0.f, then slab 0, 1, ...), so the
+// slab_reduce_body's order and form (0.f, then slab 0, 1, ...), so the
 // separate reduce launch and the write and re-read of the summed M go away and
 // the result keeps its bits.
 //
