@@ -28,7 +28,9 @@ at::Tensor conv2d_fwd(const at::Tensor&, const at::Tensor&, c10::optional<at::Te
 at::Tensor conv2d_bwd_data(const at::Tensor&, const at::Tensor&, int, int, int, int);
 at::Tensor conv2d_bwd_weight(const at::Tensor&, const at::Tensor&, int, int, int, int);
 at::Tensor conv2d_bwd_bias(const at::Tensor&);
-std::string conv_route(const std::string&, int, int, int, int, int, int, int, int);
+std::string conv_route(const std::string&, int, int, int, int, int, int, int, int,
+                       int);
+std::vector<int64_t> fast_div_eval(int64_t, int64_t, std::vector<int64_t>);
 // norm.hip
 std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor&,
                                          c10::optional<at::Tensor>,
@@ -117,6 +119,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum_f32", &slk::colsum_f32);
   m.def("matmul_f32_slab_count", &slk::matmul_f32_slab_count, py::arg("nb"),
         py::arg("M"), py::arg("N"), py::arg("K"));
+  m.def("fast_div_eval", &slk::fast_div_eval, py::arg("d"), py::arg("max_n"),
+        py::arg("ns"));
   m.def("conv2d_wino", &slk::conv2d_wino, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("pad") = 1,
         py::arg("flip") = false);
@@ -145,7 +149,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_bias", &slk::conv2d_bwd_bias);
   m.def("conv_route", &slk::conv_route, py::arg("op"), py::arg("B"),
         py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"), py::arg("K"),
-        py::arg("stride"), py::arg("pad"));
+        py::arg("stride"), py::arg("pad"), py::arg("KW") = 0);
   m.def("bn2d_stats_fused", &slk::bn2d_stats_fused);
   m.def("bn2d_fwd", &slk::bn2d_fwd);
   m.def("bn2d_bwd", &slk::bn2d_bwd, py::arg("x"), py::arg("gy"),

@@ -88,20 +88,29 @@ __device__ __forceinline__ bool slk_pool_takes(float v, float best) {
   return v > best || v != v;
 }
 
-// Fast integer division by a runtime constant (one 64-bit mul + shift).
-// Valid for dividend < 2^24 and divisor < 2^16 (all tensor-index math here):
-// m = floor(2^40/d)+1; q = (n*m) >> 40 == n/d exactly when n*d < 2^40.
+// Fast integer division by a runtime constant (one 64-bit mul + shift):
+// m = floor(2^40/d)+1; q = (n*m) >> 40.  With 2^40 = d*f + r this is
+// floor(n/d + n*(d-r)/(d*2^40)), which equals floor(n/d) for every n <= max_n
+// whenever max_n*d < 2^40 (the excess stays under 1/d) and max_n*m fits 64
+// bits (for d < 2^8 the tighter of the two: d = 1 holds up to 2^24 - 1).
+// Past that range a quotient can come out one too large (d = 2^20: first at
+// n = 2^21 - 1) and mod() then wraps to an index far outside the tensor, so a
+// FastDiv is only ever filled by fast_div() (torch_util.h), which is given the
+// largest dividend the kernel will form and refuses a pair outside the range.
 struct FastDiv {
   unsigned d;
   unsigned long long m;
-  void init(unsigned d_) {
-    d = d_ == 0 ? 1 : d_;
-    m = (0x10000000000ull / d) + 1;
+  // is div(n) == n / d for every n in [0, max_n]?  (max_n < 2^31: the
+  // kernels form their dividends as int)
+  static bool covers(unsigned long long d, unsigned long long max_n) {
+    if (d == 0 || d >= (1ull << 32) || max_n >= (1ull << 31)) return false;
+    const unsigned long long m = (0x10000000000ull / d) + 1;
+    return max_n * d < 0x10000000000ull && max_n <= ~0ull / m;
   }
-  __device__ __forceinline__ unsigned div(unsigned n) const {
+  __host__ __device__ __forceinline__ unsigned div(unsigned n) const {
     return (unsigned)(((unsigned long long)n * m) >> 40);
   }
-  __device__ __forceinline__ unsigned mod(unsigned n, unsigned q) const {
+  __host__ __device__ __forceinline__ unsigned mod(unsigned n, unsigned q) const {
     return n - q * d;
   }
 };

@@ -391,18 +391,33 @@ static ConvShape conv_shape(int B, int Ci, int H, int W, int Co, int KH, int KW,
   return {B, Ci, H, W, Co, KH, KW, stride, pad};
 }
 
-static ConvGeom make_geom(const ConvShape& s) {
+// The geometry and its dividers for one direction's kernel.  Largest dividend
+// per divider, from the gathers and stores above (the core clamps m, n and k
+// to M-1, N-1 and K-1):
+//   forward     d_ohow: n < B*OH*OW (prepB, store)  d_ow: rem < OH*OW
+//               d_khkw: k < Ci*KH*KW                d_kw: r < KH*KW
+//   bwd-data    d_hw:   n < B*H*W (prepB, store)    d_w:  rem < H*W
+//               d_khkw: k < Co*KH*KW                d_kw: r < KH*KW
+//   bwd-weight  d_ohow: k < B*OH*OW (prepK, loadA, loadB)  d_ow: rem < OH*OW
+//               d_khkw: n < Ci*KH*KW (prepB)        d_kw: r < KH*KW
+// A divider the direction does not use is filled without a dividend.
+enum class ConvDir { Fwd, BwdData, BwdWeight };
+
+static ConvGeom make_geom(const ConvShape& s, ConvDir dir, const char* op) {
   ConvGeom g;
   g.B = s.B; g.Ci = s.Ci; g.H = s.H; g.W = s.W; g.Co = s.Co; g.KH = s.KH;
   g.KW = s.KW; g.stride = s.stride; g.pad = s.pad;
   g.OH = s.OH();
   g.OW = s.OW();
-  g.d_ohow.init(g.OH * g.OW);
-  g.d_ow.init(g.OW);
-  g.d_hw.init(g.H * g.W);
-  g.d_w.init(g.W);
-  g.d_khkw.init(g.KH * g.KW);
-  g.d_kw.init(g.KW);
+  const long ohow = (long)g.OH * g.OW, hw = (long)g.H * g.W;
+  const long khkw = (long)g.KH * g.KW;
+  const bool bd = dir == ConvDir::BwdData;
+  g.d_ohow = fast_div(ohow, bd ? -1 : s.B * ohow - 1, op);
+  g.d_ow = fast_div(g.OW, bd ? -1 : ohow - 1, op);
+  g.d_hw = fast_div(hw, bd ? s.B * hw - 1 : -1, op);
+  g.d_w = fast_div(g.W, bd ? hw - 1 : -1, op);
+  g.d_khkw = fast_div(khkw, (bd ? s.Co : s.Ci) * khkw - 1, op);
+  g.d_kw = fast_div(g.KW, khkw - 1, op);
   return g;
 }
 
@@ -507,7 +522,7 @@ at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
   }
   auto xc = x.contiguous();
   auto wc = w.contiguous();
-  const ConvGeom geo = make_geom(s);
+  const ConvGeom geo = make_geom(s, ConvDir::Fwd, "conv2d_fwd");
   const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
   return direct_gemm<ConvFwdGather>(
       geo, geo.Co, geo.B * geo.OH * geo.OW, geo.Ci * geo.KH * geo.KW,
@@ -536,7 +551,7 @@ at::Tensor conv2d_bwd_data(const at::Tensor& gy, const at::Tensor& w, int stride
   }
   auto gyc = gy.contiguous();
   auto wc = w.contiguous();
-  const ConvGeom geo = make_geom(s);
+  const ConvGeom geo = make_geom(s, ConvDir::BwdData, "conv2d_bwd_data");
   return direct_gemm<ConvBwdDataGather>(
       geo, geo.Ci, geo.B * H * W, geo.Co * geo.KH * geo.KW,
       {geo.B, geo.Ci, H, W}, gy.options(), wc.data_ptr<float>(),
@@ -563,7 +578,8 @@ at::Tensor conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x, int KH,
   }
   auto gyc = gy.contiguous();
   auto xc = x.contiguous();
-  const ConvGeom geo = make_geom(s);
+  const ConvGeom geo =
+      make_geom(s, ConvDir::BwdWeight, "conv2d_bwd_weight");
   const int N = geo.Ci * KH * KW;
   const bool fast = (geo.OH * geo.OW) % SLK_BK == 0;
   return direct_gemm<ConvBwdWeightGather>(
@@ -606,10 +622,12 @@ std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>> conv2d_bwd(
 }
 
 // which kernel the wrappers above would run for a conv shape, at this
-// process's SLK_WINO level (launches nothing; tests pin the table with it)
+// process's SLK_WINO level (launches nothing; tests pin the table with it).
+// The kernel is K x K, or K x KW where KW > 0 is given.
 std::string conv_route(const std::string& op, int B, int Ci, int H, int W,
-                       int Co, int K, int stride, int pad) {
-  const ConvShape s = conv_shape(B, Ci, H, W, Co, K, K, stride, pad);
+                       int Co, int K, int stride, int pad, int KW) {
+  const ConvShape s =
+      conv_shape(B, Ci, H, W, Co, K, KW > 0 ? KW : K, stride, pad);
   if (op == "fwd") return conv_route_name(route_fwd(s, wino_level()));
   if (op == "bwd_data") return conv_route_name(route_bwd_data(s, wino_level()));
   TORCH_CHECK(op == "bwd_weight", "conv_route: op must be fwd, bwd_data or "
@@ -617,35 +635,52 @@ std::string conv_route(const std::string& op, int B, int Ci, int H, int W,
   return conv_route_name(route_bwd_weight(s, wino_level()));
 }
 
+// FastDiv as the kernels use it, evaluated on the host: the quotients div()
+// gives for ns under the divider fast_div(d, max_n) fills (launches nothing;
+// tests compare them with n / d up to the checked limit)
+std::vector<int64_t> fast_div_eval(int64_t d, int64_t max_n,
+                                   std::vector<int64_t> ns) {
+  const FastDiv f = fast_div(d, max_n, "fast_div_eval");
+  for (auto& n : ns) {
+    TORCH_CHECK(n >= 0 && n <= max_n, "fast_div_eval: dividend ", n,
+                " outside [0, max_n]");
+    n = f.div((unsigned)n);
+  }
+  return ns;
+}
+
 // per-channel sum of gy over (B, OH, OW) -> conv bias gradient
-// (chunk slabs + finalize reduce: no zero-init, no atomics)
+// (chunk slabs + finalize reduce: no zero-init, no atomics).  Summed in double
+// and rounded once, as the BatchNorm sums are: a float sum's rounding is set
+// by its partial sums, and a channel whose terms cancel (25 terms of size 1
+// summing to 0.06) came out 6 ulps off where torch was 1 off.
 __global__ void conv_bias_grad_kernel(const float* __restrict__ gy,
-                                      float* __restrict__ slab, int B, int C,
+                                      double* __restrict__ slab, int B, int C,
                                       int HW) {
-  __shared__ float scratch[16];
+  __shared__ double scratch[16];
   const int c = blockIdx.x;
   const int total = B * HW;
   const int per = (total + gridDim.y - 1) / gridDim.y;
   const int lo = blockIdx.y * per;
   const int hi = min(total, lo + per);
-  float acc = 0.f;
+  double acc = 0.0;
   for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     const int b = i / HW;
     const int r = i - b * HW;
-    acc += gy[((long)b * C + c) * HW + r];
+    acc += (double)gy[((long)b * C + c) * HW + r];
   }
-  float total_s = slk_block_sum(acc, scratch);
+  const double total_s = slk_block_sum(acc, scratch);
   if (threadIdx.x == 0) slab[(long)blockIdx.y * C + c] = total_s;
 }
 
-__global__ void conv_bias_finalize_kernel(const float* __restrict__ slab,
+__global__ void conv_bias_finalize_kernel(const double* __restrict__ slab,
                                           int chunks, float* __restrict__ gb,
                                           int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  float s = 0.f;
+  double s = 0.0;
   for (int k = 0; k < chunks; ++k) s += slab[(long)k * C + c];
-  gb[c] = s;
+  gb[c] = (float)s;
 }
 
 at::Tensor conv2d_bwd_bias(const at::Tensor& gy) {
@@ -653,13 +688,13 @@ at::Tensor conv2d_bwd_bias(const at::Tensor& gy) {
   const int B = gy.size(0), C = gy.size(1), HW = gy.size(2) * gy.size(3);
   auto gb = at::empty({C}, gy.options());
   const int chunks = reduce_chunks((long)B * HW);
-  auto slab = at::empty({chunks, C}, gy.options());
+  auto slab = at::empty({chunks, C}, gy.options().dtype(at::kDouble));
   auto stream = c10::hip::getCurrentHIPStream().stream();
   hipLaunchKernelGGL(conv_bias_grad_kernel, dim3(C, (uint32_t)chunks), dim3(256),
-                     0, stream, gyc.data_ptr<float>(), slab.data_ptr<float>(), B, C,
+                     0, stream, gyc.data_ptr<float>(), slab.data_ptr<double>(), B, C,
                      HW);
   hipLaunchKernelGGL(conv_bias_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256),
-                     0, stream, slab.data_ptr<float>(), chunks,
+                     0, stream, slab.data_ptr<double>(), chunks,
                      gb.data_ptr<float>(), C);
   return gb;
 }

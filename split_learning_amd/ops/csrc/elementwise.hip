@@ -1,11 +1,7 @@
 // Elementwise / pooling / dropout / embedding kernels (fp32, grid-stride).
 // Memory-bound ops: float4-vectorized main loop with scalar tail (CDNA guide
 // Appendix B: elementwise target is the HBM ceiling).
-#include <torch/extension.h>
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
-
-#include "common.h"
+#include "torch_util.h"
 
 namespace slk {
 
@@ -269,10 +265,9 @@ std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x) {
   auto idx = at::empty({B, C, OH, OW}, x.options().dtype(at::kByte));
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const long total = (long)B * C * OH * OW;
-  FastDiv d_ohow, d_ow;
-  d_ohow.init(OH * OW);
-  d_ow.init(OW);
-  TORCH_CHECK(total <= (1l << 24), "maxpool_fwd: FastDiv range");
+  // maxpool_fwd_kernel: i < total, rem < OH*OW
+  const FastDiv d_ohow = fast_div((long)OH * OW, total - 1, "maxpool2x2_fwd");
+  const FastDiv d_ow = fast_div(OW, (long)OH * OW - 1, "maxpool2x2_fwd");
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_grid(total, 256, 1)), dim3(256), 0,
                      stream, x.data_ptr<float>(), y.data_ptr<float>(),
                      idx.data_ptr<uint8_t>(), B * C, H, W, OH, OW, d_ohow, d_ow);
@@ -284,10 +279,9 @@ at::Tensor maxpool2x2_bwd(const at::Tensor& gy, const at::Tensor& idx, int H, in
   auto gx = at::empty({B, C, H, W}, gy.options());
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const long total = (long)B * C * H * W;
-  FastDiv d_hw, d_w;
-  d_hw.init(H * W);
-  d_w.init(W);
-  TORCH_CHECK(total <= (1l << 24), "maxpool_bwd: FastDiv range");
+  // maxpool_bwd_kernel: i < total, rem < H*W
+  const FastDiv d_hw = fast_div((long)H * W, total - 1, "maxpool2x2_bwd");
+  const FastDiv d_w = fast_div(W, (long)H * W - 1, "maxpool2x2_bwd");
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_grid(total, 256, 1)), dim3(256), 0,
                      stream, gy.data_ptr<float>(), idx.data_ptr<uint8_t>(),
                      gx.data_ptr<float>(), B * C, H, W, OH, OW, d_hw, d_w);

@@ -127,7 +127,17 @@ at::Tensor matmul_f32(const at::Tensor& a, const at::Tensor& b, bool ta, bool tb
 
   at::Tensor c;
   if (out.has_value()) {
+    // the store writes c as a dense row-major [nb, M, N] block
     c = *out;
+    const std::vector<int64_t> want =
+        a.dim() == 3 ? std::vector<int64_t>{a.size(0), M, N}
+                     : std::vector<int64_t>{M, N};
+    TORCH_CHECK(c.is_cuda() && c.device() == a.device() &&
+                c.scalar_type() == at::kFloat,
+                "matmul_f32: out must be a fp32 tensor on the operands' GPU");
+    TORCH_CHECK(c.sizes() == at::IntArrayRef(want), "matmul_f32: out has shape ",
+                c.sizes(), ", the product is ", at::IntArrayRef(want));
+    TORCH_CHECK(c.is_contiguous(), "matmul_f32: out must be contiguous");
   } else {
     c = a.dim() == 3 ? at::empty({a.size(0), M, N}, a.options())
                      : at::empty({M, N}, a.options());

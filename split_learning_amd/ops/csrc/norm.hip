@@ -43,14 +43,19 @@ struct PoolGeom {
   FastDiv d_w, d_ow, d_ohow;
 };
 
-static inline PoolGeom pool_geom(int H, int W) {
+// planes: how many pooled planes the op's kernels index as one range through
+// d_ohow (B in bn_fwd_one_kernel, B*C in bn_pool_fwd_kernel, 0 in the
+// backward, which decodes r < H*W through d_w alone); d_ow decodes an index
+// within one pooled plane.
+static inline PoolGeom pool_geom(int H, int W, long planes, const char* op) {
   PoolGeom pg;
   pg.W = W;
   pg.OH = H / 2;
   pg.OW = W / 2;
-  pg.d_w.init(W);
-  pg.d_ow.init(pg.OW);
-  pg.d_ohow.init(pg.OH * pg.OW);
+  const long ohow = (long)pg.OH * pg.OW;
+  pg.d_w = fast_div(W, (long)H * W - 1, op);
+  pg.d_ow = fast_div(pg.OW, ohow - 1, op);
+  pg.d_ohow = fast_div(ohow, planes * ohow - 1, op);
   return pg;
 }
 
@@ -639,8 +644,8 @@ std::vector<at::Tensor> bn2d_stats_fused(const at::Tensor& x,
   auto invstd = at::empty({C}, x.options());
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int chunks = reduce_chunks((long)B * HW);
-  FastDiv d_hw;
-  d_hw.init(HW);
+  // a channel's (b, hw) range: i < B*HW
+  const FastDiv d_hw = fast_div(HW, (long)B * HW - 1, "bn2d_stats_fused");
   if (chunks == 1) {
     hipLaunchKernelGGL(bn_stats_one_kernel, dim3(C), dim3(256), 0, stream,
                        x.data_ptr<float>(), mean.data_ptr<float>(),
@@ -672,10 +677,9 @@ at::Tensor bn2d_fwd(const at::Tensor& x, const at::Tensor& mean,
   const int C = x.size(1), HW = x.size(2) * x.size(3);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = (int)std::min<long>((total + 255) / 256, 2048);
-  FastDiv d_hw, d_c;
-  d_hw.init(HW);
-  d_c.init(C);
-  TORCH_CHECK(total <= (1l << 24), "bn_fwd: FastDiv range");
+  // bn_fwd_kernel: i < total gives bc < B*C
+  const FastDiv d_hw = fast_div(HW, total - 1, "bn2d_fwd");
+  const FastDiv d_c = fast_div(C, (long)x.size(0) * C - 1, "bn2d_fwd");
   hipLaunchKernelGGL(bn_fwd_kernel, dim3(grid), dim3(256), 0, stream,
                      x.data_ptr<float>(), y.data_ptr<float>(),
                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
@@ -700,22 +704,28 @@ std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor& x, const at::Tensor& ga
               x.scalar_type() == at::kFloat, "bn2d_train_fwd: x");
   const int B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int HW = H * W;
-  TORCH_CHECK(x.numel() <= (1l << 24), "bn2d_train_fwd: FastDiv range");
   TORCH_CHECK(!pool || (relu && H % 2 == 0 && W % 2 == 0 && HW > 0),
               "bn2d_train_fwd: pool needs relu and even H, W");
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const PoolGeom pg = pool ? pool_geom(H, W) : PoolGeom{};
+  const bool one = reduce_chunks((long)B * HW) == 1;
+  // every divider of the op before its first launch.  One kernel: a block
+  // walks its channel's B planes (i < B*HW, pooled j < B*OH*OW); chunked: the
+  // apply kernels walk the whole tensor (bn2d_fwd, bn_pool_fwd_kernel)
+  const PoolGeom pg =
+      pool ? pool_geom(H, W, one ? B : (long)B * C, "bn2d_train_fwd")
+           : PoolGeom{};
+  const FastDiv d_hw = fast_div(
+      HW, (one || pool ? (long)B * HW : x.numel()) - 1, "bn2d_train_fwd");
+  const FastDiv d_c = fast_div(C, (long)B * C - 1, "bn2d_train_fwd");
   at::Tensor y, idx;
   if (pool) {
     y = at::empty({B, C, H / 2, W / 2}, x.options());
     idx = at::empty({B, C, H / 2, W / 2}, x.options().dtype(at::kByte));
   }
-  if (reduce_chunks((long)B * HW) == 1) {
+  if (one) {
     auto mean = at::empty({C}, x.options());
     auto invstd = at::empty({C}, x.options());
     if (!pool) y = at::empty_like(x);
-    FastDiv d_hw;
-    d_hw.init(HW);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(C), dim3(256), 0, stream,
                          x.data_ptr<float>(), y.data_ptr<float>(),
@@ -738,8 +748,6 @@ std::vector<at::Tensor> bn2d_train_fwd(const at::Tensor& x, const at::Tensor& ga
                      stats[1]};
   const long ptotal = y.numel();
   int grid = (int)std::min<long>((ptotal + 255) / 256, 2048);
-  FastDiv d_c;
-  d_c.init(C);
   hipLaunchKernelGGL(bn_pool_fwd_kernel, dim3(grid), dim3(256), 0, stream,
                      x.data_ptr<float>(), y.data_ptr<float>(),
                      idx.data_ptr<uint8_t>(), stats[0].data_ptr<float>(),
@@ -763,7 +771,13 @@ static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tens
   const uint8_t* ip = pool ? idx->data_ptr<uint8_t>() : nullptr;
   const int B = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   const long total = x.numel();
-  TORCH_CHECK(total <= (1l << 24), "bn_bwd: FastDiv range");
+  const int rchunks = reduce_chunks((long)B * HW);
+  const bool one = rchunks == 1 && one_launch && training;
+  // a block of the reduce (and of the one-launch kernel) walks its channel's
+  // i < B*HW; bn_bwd_dx_kernel walks i < total, which gives bc < B*C
+  const FastDiv d_hw =
+      fast_div(HW, (one ? (long)B * HW : total) - 1, "bn2d_bwd");
+  const FastDiv d_c = fast_div(C, (long)B * C - 1, "bn2d_bwd");
   PoolGeom pg{};
   if (pool) {
     const int H = x.size(2), W = x.size(3);
@@ -771,7 +785,7 @@ static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tens
                 "bn_bwd: pooled form needs training mode, relu_y and even H, W");
     TORCH_CHECK(gy.numel() * 4 == total && relu_y->numel() * 4 == total &&
                 idx->numel() * 4 == total, "bn_bwd: pooled operand shapes");
-    pg = pool_geom(H, W);
+    pg = pool_geom(H, W, 0, "bn2d_bwd");
   } else {
     TORCH_CHECK(gy.numel() == total && (ry == nullptr || relu_y->numel() == total),
                 "bn_bwd: operand shapes");
@@ -780,11 +794,8 @@ static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tens
   auto sum_gy_xhat = at::empty({C}, x.options());
   auto gx = at::empty_like(x);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int rchunks = reduce_chunks((long)B * HW);
   const float inv_n = 1.0f / (float)((long)B * HW);
-  FastDiv d_hw;
-  d_hw.init(HW);
-  if (rchunks == 1 && one_launch && training) {
+  if (one) {
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(C), dim3(256), 0, stream,
                          x.data_ptr<float>(), gy.data_ptr<float>(), ry, ip,
@@ -818,8 +829,6 @@ static std::vector<at::Tensor> bn2d_bwd_impl(const at::Tensor& x, const at::Tens
                        sum_gy.data_ptr<float>(), sum_gy_xhat.data_ptr<float>(), C);
   }
   int grid = (int)std::min<long>((total + 255) / 256, 2048);
-  FastDiv d_c;
-  d_c.init(C);
   auto launch_dx = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream,
                        x.data_ptr<float>(), gy.data_ptr<float>(), ry, ip,

@@ -19,6 +19,24 @@ static inline at::Tensor zeroed(at::IntArrayRef sizes, const at::TensorOptions& 
   return t;
 }
 
+// The one way to fill a FastDiv (common.h): divisor d (0 stands for an empty
+// dimension and divides as 1) and the largest dividend the op's kernels will
+// pass to div(); max_n < 0 means none (a divider the launch does not use).
+// Refuses, before anything is launched, a pair whose quotients are not exact.
+static inline FastDiv fast_div(long d, long max_n, const char* op) {
+  if (d == 0) d = 1;
+  if (max_n < 0) max_n = 0;
+  TORCH_CHECK(d > 0 && FastDiv::covers((unsigned long long)d,
+                                       (unsigned long long)max_n),
+              op, ": index ", max_n, " divided by ", d,
+              " is outside FastDiv's exact range (needs index * divisor < 2^40"
+              " and index < 2^31); use a smaller batch or image");
+  FastDiv f;
+  f.d = (unsigned)d;
+  f.m = (0x10000000000ull / f.d) + 1;
+  return f;
+}
+
 // chunk count for per-channel reductions over (B, HW) that write chunk slabs
 // and finalize in fixed order (BatchNorm statistics, conv bias gradient)
 static inline int reduce_chunks(long per_channel) {

@@ -265,14 +265,19 @@ struct WinoTiles {
   FastDiv d_T, d_thw, d_tw;
 };
 
-static WinoTiles wino_tiles(int B, int OH, int OW) {
+// chans: the most channels any transform kernel of the op spreads over the
+// tiles (d_T decodes an index below chans * T); 0 for the fused kernels, which
+// take their tile index from the grid and use d_thw and d_tw only.  Those two
+// decode a tile below T and a tile of one image below tH * tW.
+static WinoTiles wino_tiles(int B, int OH, int OW, int chans, const char* who) {
   WinoTiles g;
   g.tH = OH / 2;
   g.tW = OW / 2;
   g.T = B * g.tH * g.tW;
-  g.d_T.init(g.T);
-  g.d_thw.init(g.tH * g.tW);
-  g.d_tw.init(g.tW);
+  const long thw = (long)g.tH * g.tW;
+  g.d_T = fast_div(g.T, (long)chans * B * thw - 1, who);
+  g.d_thw = fast_div(thw, B * thw - 1, who);
+  g.d_tw = fast_div(g.tW, thw - 1, who);
   return g;
 }
 
@@ -303,7 +308,7 @@ at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(x.size(1) == Ci, "wino: channel mismatch");
   const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
   TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino: even output dims only");
-  const WinoTiles g = wino_tiles(B, OH, OW);
+  const WinoTiles g = wino_tiles(B, OH, OW, std::max(Ci, Co), "conv2d_wino");
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   auto U = at::empty({16, Co, Ci}, x.options());
@@ -345,7 +350,8 @@ at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
   TORCH_CHECK(OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2,
               "wino_bwdw geometry");
   TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino_bwdw: even output dims only");
-  const WinoTiles g = wino_tiles(B, OH, OW);
+  const WinoTiles g =
+      wino_tiles(B, OH, OW, std::max(Ci, Co), "conv2d_wino_bwdw");
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   auto Wg = at::empty({16, Co, g.T}, x.options());
@@ -817,7 +823,7 @@ static WinoFusedArgs wino_fused_args(int B, int Ci, int H, int W, int Co,
   a.B = B; a.Ci = Ci; a.H = H; a.W = W; a.Co = Co; a.pad = pad; a.CW = CW;
   a.OH = H + 2 * pad - 2;
   a.OW = W + 2 * pad - 2;
-  const WinoTiles g = wino_tiles(B, a.OH, a.OW);
+  const WinoTiles g = wino_tiles(B, a.OH, a.OW, 0, who);
   TORCH_CHECK(Co % 32 == 0 && g.T % 32 == 0 && Ci % 8 == 0 && a.OH % 2 == 0 &&
               a.OW % 2 == 0 && g.T > 0, who, " shape requirements");
   a.tH = g.tH; a.tW = g.tW; a.d_thw = g.d_thw; a.d_tw = g.d_tw;
@@ -846,7 +852,7 @@ static WinoBwdwArgs wino_bwdw_args(int B, int Ci, int H, int W, int Co, int pad,
   a.OW = W + 2 * pad - 2;
   TORCH_CHECK(a.OH % 2 == 0 && a.OW % 2 == 0 && Co % 32 == 0 && Ci % 32 == 0 &&
               Co > 0 && Ci > 0, who, " shape requirements");
-  const WinoTiles g = wino_tiles(B, a.OH, a.OW);
+  const WinoTiles g = wino_tiles(B, a.OH, a.OW, 0, who);
   a.tH = g.tH; a.tW = g.tW; a.d_thw = g.d_thw; a.d_tw = g.d_tw;
   const WinoSplit sp = wino_bwdw_split(Co, Ci, g.T);
   a.t_per = sp.per;

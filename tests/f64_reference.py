@@ -1,10 +1,11 @@
-"""Plain float64 definitions of the small ops, on the CPU.
+"""Plain float64 definitions of the ops, on the CPU.
 
 Each function is the textbook formula in torch double, a few lines, with no
 call into the package under test and no call to the torch op it stands for
 (tests/test_f64_reference.py checks each against that torch op in double).
 Inputs are fp32 test inputs; every function upcasts what it is given.
-tests/test_small_kernels_f64_gpu.py compares the HIP kernels with these.
+tests/test_small_kernels_f64_gpu.py and tests/test_gemm_conv_f64_gpu.py
+compare the HIP kernels with these.
 """
 
 import math
@@ -173,6 +174,89 @@ def maxpool2x2(x):
     B, C, H, W = x.shape
     w = x[:, :, :H // 2 * 2, :W // 2 * 2].reshape(B, C, H // 2, 2, W // 2, 2)
     return w.permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4).max(dim=-1).values
+
+
+# ---------------- matmul / linear ----------------
+
+def matmul(a, b, trans_a=False, trans_b=False):
+    """C[..., m, n] = sum_k A[..., m, k] B[..., k, n], one rank-1 term per k."""
+    a, b = _d(a), _d(b)
+    if trans_a:
+        a = a.transpose(-1, -2)
+    if trans_b:
+        b = b.transpose(-1, -2)
+    c = torch.zeros(*a.shape[:-1], b.shape[-1], dtype=torch.float64)
+    for k in range(a.shape[-1]):
+        c += a[..., :, k, None] * b[..., k, None, :]
+    return c
+
+
+def linear(x, w, bias=None):
+    """y[m, n] = sum_k x[m, k] w[n, k] + bias[n]"""
+    y = matmul(x, w, trans_b=True)
+    return y if bias is None else y + _d(bias)
+
+
+# ---------------- conv2d ----------------
+# x [B, Ci, H, W], w [Co, Ci, KH, KW], y [B, Co, OH, OW] with
+# OH = (H + 2 pad - KH) // stride + 1; tap (kh, kw) of output (oh, ow) reads
+# the zero-padded input at (oh stride + kh, ow stride + kw).
+
+def _taps(w_shape, OH, OW, stride):
+    """(kh, kw, row slice, column slice) of the padded plane for every tap"""
+    for kh in range(w_shape[2]):
+        for kw in range(w_shape[3]):
+            yield (kh, kw, slice(kh, kh + (OH - 1) * stride + 1, stride),
+                   slice(kw, kw + (OW - 1) * stride + 1, stride))
+
+
+def _padded(x, pad):
+    B, C, H, W = x.shape
+    xp = torch.zeros(B, C, H + 2 * pad, W + 2 * pad, dtype=torch.float64)
+    xp[:, :, pad:pad + H, pad:pad + W] = x
+    return xp
+
+
+def conv_out_hw(H, W, KH, KW, stride, pad):
+    return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+
+
+def conv2d(x, w, bias=None, stride=1, pad=0):
+    x, w = _d(x), _d(w)
+    OH, OW = conv_out_hw(x.shape[2], x.shape[3], w.shape[2], w.shape[3], stride, pad)
+    xp = _padded(x, pad)
+    y = torch.zeros(x.shape[0], w.shape[0], OH, OW, dtype=torch.float64)
+    for kh, kw, rows, cols in _taps(w.shape, OH, OW, stride):
+        # [B, 1, Ci, OH, OW] * [1, Co, Ci, 1, 1] summed over Ci
+        y += (xp[:, None, :, rows, cols] * w[None, :, :, kh, kw, None, None]).sum(dim=2)
+    return y if bias is None else y + _chan(_d(bias))
+
+
+def conv2d_bwd_data(gy, w, stride, pad, H, W):
+    """gx: every tap scatters gy * w back to the input position it read."""
+    gy, w = _d(gy), _d(w)
+    OH, OW = gy.shape[2], gy.shape[3]
+    gxp = torch.zeros(gy.shape[0], w.shape[1], H + 2 * pad, W + 2 * pad,
+                      dtype=torch.float64)
+    for kh, kw, rows, cols in _taps(w.shape, OH, OW, stride):
+        # [B, Co, 1, OH, OW] * [1, Co, Ci, 1, 1] summed over Co
+        gxp[:, :, rows, cols] += (gy[:, :, None] * w[None, :, :, kh, kw, None, None]).sum(dim=1)
+    return gxp[:, :, pad:pad + H, pad:pad + W]
+
+
+def conv2d_bwd_weight(gy, x, KH, KW, stride, pad):
+    gy, x = _d(gy), _d(x)
+    OH, OW = gy.shape[2], gy.shape[3]
+    xp = _padded(x, pad)
+    gw = torch.zeros(gy.shape[1], x.shape[1], KH, KW, dtype=torch.float64)
+    for kh, kw, rows, cols in _taps(gw.shape, OH, OW, stride):
+        # [B, Co, 1, OH, OW] * [B, 1, Ci, OH, OW] summed over B, OH, OW
+        gw[:, :, kh, kw] = (gy[:, :, None] * xp[:, None, :, rows, cols]).sum(dim=(0, 3, 4))
+    return gw
+
+
+def conv2d_bwd_bias(gy):
+    return _d(gy).sum(dim=(0, 2, 3))
 
 
 # ---------------- embedding ----------------

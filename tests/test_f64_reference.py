@@ -1,4 +1,5 @@
-"""The float64 yardstick of tests/test_small_kernels_f64_gpu.py, checked on the
+"""The float64 yardstick of tests/test_small_kernels_f64_gpu.py and
+tests/test_gemm_conv_f64_gpu.py, checked on the
 CPU against torch's own double-precision ops.  Both sides are float64, so
 they agree to a few ulps of double; 1e-12 relative to the largest value leaves
 room for a different summation order and nothing else."""
@@ -174,3 +175,53 @@ def test_embedding(padding_idx):
     y.backward(gy.double())
     assert torch.equal(R.embedding(ids, w), y.detach())
     _same(R.embedding_bwd(ids, gy, 11, padding_idx), wd.grad, "embedding gw")
+
+
+@pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True),
+                                   (True, True)])
+def test_matmul(ta, tb):
+    g = _gen(9)
+    for batch in ((), (3,)):
+        a = torch.randn(*batch, *((7, 5) if ta else (5, 7)), generator=g)
+        b = torch.randn(*batch, *((4, 7) if tb else (7, 4)), generator=g)
+        ad = a.double().transpose(-1, -2) if ta else a.double()
+        bd = b.double().transpose(-1, -2) if tb else b.double()
+        _same(R.matmul(a, b, ta, tb), torch.matmul(ad, bd), f"matmul {batch}")
+
+
+def test_linear():
+    g = _gen(10)
+    x, w, b = (torch.randn(6, 9, generator=g), torch.randn(4, 9, generator=g),
+               torch.randn(4, generator=g))
+    _same(R.linear(x, w, b), F.linear(x.double(), w.double(), b.double()), "linear")
+    _same(R.linear(x, w), F.linear(x.double(), w.double()), "linear, no bias")
+
+
+# (B, Ci, H, W, Co, KH, KW, stride, pad): every tap shape and stride of
+# tests/test_gemm_conv_f64_gpu.py, and strides that leave input rows unread
+CONV_REF_CASES = [
+    (2, 3, 7, 6, 4, 3, 3, 1, 1), (2, 3, 7, 6, 4, 3, 3, 2, 1), (1, 5, 4, 5, 2, 1, 1, 1, 0),
+    (2, 2, 8, 12, 3, 4, 4, 4, 0), (1, 2, 9, 7, 3, 5, 5, 1, 2), (2, 2, 11, 9, 3, 7, 7, 2, 3),
+    (2, 3, 6, 7, 2, 2, 2, 2, 0), (2, 3, 7, 8, 2, 3, 3, 3, 1), (1, 2, 5, 7, 3, 1, 3, 1, 1),
+    (1, 2, 7, 5, 3, 3, 1, 1, 0), (2, 2, 1, 9, 3, 1, 3, 1, 1), (2, 2, 5, 5, 3, 3, 3, 1, 2),
+]
+
+
+@pytest.mark.parametrize("case", CONV_REF_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_conv2d(case):
+    B, Ci, H, W, Co, KH, KW, s, p = case
+    g = _gen(11)
+    x = torch.randn(B, Ci, H, W, generator=g)
+    w = torch.randn(Co, Ci, KH, KW, generator=g)
+    b = torch.randn(Co, generator=g)
+    xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
+    y = F.conv2d(xd, wd, bd, stride=s, padding=p)
+    assert tuple(y.shape[2:]) == R.conv_out_hw(H, W, KH, KW, s, p)
+    gy = torch.randn(y.shape, generator=g)
+    y.backward(gy.double())
+    _same(R.conv2d(x, w, b, s, p), y, "conv2d")
+    _same(R.conv2d(x, w, None, s, p), F.conv2d(xd, wd, None, stride=s, padding=p),
+          "conv2d, no bias")
+    _same(R.conv2d_bwd_data(gy, w, s, p, H, W), xd.grad, "conv2d gx")
+    _same(R.conv2d_bwd_weight(gy, x, KH, KW, s, p), wd.grad, "conv2d gw")
+    _same(R.conv2d_bwd_bias(gy), bd.grad, "conv2d gb")

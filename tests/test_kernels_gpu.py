@@ -9,8 +9,10 @@ Not every code path runs here.  The small kernels (optimizers, cross-entropy,
 softmax, LayerNorm, BatchNorm, activations, maxpool, embedding, dropout) are
 tested at their edges (vector body/tail, grid caps, multi-chunk and
 multi-block paths, special values, NaN propagation) against a float64
-reference in tests/test_small_kernels_f64_gpu.py; conv and attention have
-their own modules.
+reference in tests/test_small_kernels_f64_gpu.py, the GEMM core and the
+direct convolutions (tile, K-step and split edges, every specialisation) in
+tests/test_gemm_conv_f64_gpu.py; Winograd and attention have their own
+modules.
 """
 
 import pytest

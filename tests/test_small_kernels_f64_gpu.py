@@ -55,10 +55,10 @@ import torch
 import torch.nn.functional as F
 
 import f64_reference as R
+from f64_compare import EPS32, cmp as _cmp, cpu64 as _cpu64, exact as _exact
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = 2.0 ** -23
 NAN, INF = float("nan"), float("inf")
 
 
@@ -71,44 +71,11 @@ def _gen(seed):
     return torch.Generator(device="cpu").manual_seed(seed)
 
 
-def _cpu64(t):
-    return t.detach().to(device="cpu", dtype=torch.float64)
-
-
-def _cmp(family, what, kernel, torch32, ref64):
-    """the tolerance rule; NaN and inf placement must equal the reference's"""
-    k, t, r = _cpu64(kernel), _cpu64(torch32), _cpu64(ref64)
-    assert k.shape == r.shape == t.shape, f"{family} {what}: shapes"
-    nan, inf = torch.isnan(r), torch.isinf(r)
-    assert torch.equal(torch.isnan(k), nan), f"{family} {what}: NaN placement"
-    assert torch.equal(k[inf], r[inf]), f"{family} {what}: inf placement"
-    fin = ~(nan | inf)
-    if not bool(fin.any()):
-        return
-    e_kernel = float((k[fin] - r[fin]).abs().max())
-    e_torch = float((t[fin] - r[fin]).abs().max())
-    bound = 4.0 * e_torch + 4.0 * EPS32 * float(r[fin].abs().max())
-    print(f"F64 | {family} | {what} | e_kernel {e_kernel:.3e} | "
-          f"e_torch {e_torch:.3e} | bound {bound:.3e}")
-    assert e_kernel <= bound, (
-        f"{family} {what}: e_kernel {e_kernel:.3e} > bound {bound:.3e} "
-        f"(e_torch {e_torch:.3e})")
-
-
 def _same_nan_mask(ours, theirs, what):
     a, b = torch.isnan(ours).cpu(), torch.isnan(theirs).cpu()
     assert bool(b.any()), f"{what}: the torch composition shows no NaN"
     assert torch.equal(a, b), (
         f"{what}: {int(a.sum())} NaN of {a.numel()}, torch has {int(b.sum())}")
-
-
-def _exact(ours, theirs, what):
-    """exact equality; NaN equals NaN"""
-    a, b = ours.detach().cpu(), theirs.detach().cpu()
-    assert a.shape == b.shape, what
-    assert torch.equal(torch.isnan(a), torch.isnan(b)), f"{what}: NaN placement"
-    ok = (a == b) | torch.isnan(b)
-    assert bool(ok.all()), f"{what}: {int((~ok).sum())} of {a.numel()} differ"
 
 
 # ---------------- optimizers ----------------
