@@ -20,6 +20,7 @@ std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor&,
                                                    const at::Tensor&,
                                                    const at::Tensor&, int, int);
 std::tuple<int, int, int, int> conv2d_bwd_pair_splits(int, int, int, int, int, int);
+std::tuple<int, int> conv2d_wino_fused_splits(int, int, int);
 // conv2d.hip
 std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>> conv2d_bwd(
     const at::Tensor&, const at::Tensor&, const at::Tensor&, int, int, bool, bool);
@@ -146,6 +147,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_pair_splits", &slk::conv2d_bwd_pair_splits, py::arg("B"),
         py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"),
         py::arg("pad") = 1);
+  m.def("conv2d_wino_fused_splits", &slk::conv2d_wino_fused_splits,
+        py::arg("co"), py::arg("ci"), py::arg("tiles"));
   m.def("conv2d_bwd_bias", &slk::conv2d_bwd_bias);
   m.def("conv_route", &slk::conv_route, py::arg("op"), py::arg("B"),
         py::arg("Ci"), py::arg("H"), py::arg("W"), py::arg("Co"), py::arg("K"),

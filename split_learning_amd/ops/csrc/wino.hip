@@ -28,6 +28,18 @@
 //   conv2d_wino_bwdw_fused  wino_bwdw_fused_kernel, its bwd-weight twin.
 //   conv2d_bwd_pair         wino_bwd_pair_kernel: the bodies of the two fused
 //                           backward kernels in one grid.
+//
+// Non-finite inputs.  A NaN in x reaches exactly the outputs a direct conv
+// gives it: B^T and A^T mix patch rows 0..2 into output row 0 and 1..3 into
+// row 1 (columns alike), the windows of those outputs.  An inf in x makes the
+// same outputs non-finite, but they may read NaN where a direct conv reads
+// inf: the input transform holds +inf in one frequency and -inf in another
+// (d0 - d2, d2 - d1), and A^T adds them.  The weight gradient mixes the nine
+// taps of a (co, ci) pair in G^T dU G, so one non-finite x or gy value can
+// turn all nine non-finite, a tap whose window never held it included (at a
+// border a direct conv leaves that tap finite).  All of this is the
+// algorithm's, not an implementation's; tests/test_wino_f64_gpu.py pins it.
+//
 // Every transform's arithmetic is in wino_math.h, once, and each kernel here
 // calls it: that is what keeps the forms bit-identical to each other.  Each
 // fused kernel takes one argument struct (WinoFusedArgs, WinoBwdwArgs) that
@@ -294,20 +306,56 @@ static void wino_dispatch_flip(bool flip, Launch&& launch) {
   else launch(std::false_type{});
 }
 
+// Operand checks of the host entries.  The kernels take raw float pointers
+// and index them from the shapes alone, so whatever a shape promises is checked
+// here, before anything is allocated or launched.
+static void wino_check_operand(const at::Tensor& t, const at::Tensor& x,
+                               const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() &&
+              t.scalar_type() == at::kFloat && t.dim() == 4,
+              who, ": ", name, " must be a 4-D fp32 tensor on the GPU of the "
+              "other operands (got ", t.scalar_type(), ", ", t.dim(), "-D, ",
+              t.device(), ")");
+}
+
+// the flip form is the bwd-data conv of a layer padded 2 - pad, and the
+// bwd-weight forms route layers padded at most 2: past 2 nothing calls them
+static void wino_check_pad(int pad, bool at_most_2, const char* who) {
+  TORCH_CHECK(pad >= 0 && (!at_most_2 || pad <= 2), who, ": pad ", pad,
+              at_most_2 ? " outside 0..2" : " is negative");
+}
+
+// the bias pointer a kernel reads at [0, Co), or nullptr
+static const float* wino_bias_ptr(const c10::optional<at::Tensor>& bias,
+                                  const at::Tensor& x, int Co, const char* who) {
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+              bias->scalar_type() == at::kFloat && bias->dim() == 1 &&
+              bias->size(0) == Co && bias->is_contiguous(),
+              who, ": bias must be a contiguous fp32 vector of length ", Co,
+              " on the GPU of x (got ", bias->scalar_type(), " ",
+              bias->sizes(), " on ", bias->device(), ")");
+  return bias->data_ptr<float>();
+}
+
 // host entry: 3x3 stride-1 conv via F(2x2,3x3); flip=true computes the
 // bwd-data conv (weights rotated + Co/Ci transposed, pad' = 2 - pad)
 at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
                        c10::optional<at::Tensor> bias, int pad, bool flip) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat);
+  wino_check_operand(w, x, "wino", "w");
   TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, "wino: 3x3 only");
-  auto xc = x.contiguous();
-  auto wc = w.contiguous();
+  wino_check_pad(pad, flip, "wino");
   const int B = x.size(0), H = x.size(2), W = x.size(3);
   const int Co = flip ? w.size(1) : w.size(0);
   const int Ci = flip ? w.size(0) : w.size(1);
   TORCH_CHECK(x.size(1) == Ci, "wino: channel mismatch");
+  const float* bias_p = wino_bias_ptr(bias, x, Co, "wino");
   const int OH = H + 2 * pad - 2, OW = W + 2 * pad - 2;
-  TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino: even output dims only");
+  TORCH_CHECK(OH > 0 && OW > 0 && OH % 2 == 0 && OW % 2 == 0,
+              "wino: even output dims only");
+  auto xc = x.contiguous();
+  auto wc = w.contiguous();
   const WinoTiles g = wino_tiles(B, OH, OW, std::max(Ci, Co), "conv2d_wino");
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
@@ -334,22 +382,27 @@ at::Tensor conv2d_wino(const at::Tensor& x, const at::Tensor& w,
   const int out_grid = (int)std::min<long>(((long)Co * g.T + 63) / 64, 8192);
   hipLaunchKernelGGL(wino_out_kernel, dim3(out_grid), dim3(256), 0, stream,
                      Mm.data_ptr<float>(), (int)Mm.size(0), 16l * Co * g.T,
-                     y.data_ptr<float>(),
-                     bias.has_value() ? bias->data_ptr<float>() : nullptr, B,
-                     Co, OH, OW, g.tH, g.tW, g.d_T, g.d_thw, g.d_tw);
+                     y.data_ptr<float>(), bias_p, B, Co, OH, OW, g.tH, g.tW,
+                     g.d_T, g.d_thw, g.d_tw);
   return y;
 }
 
 at::Tensor conv2d_wino_bwdw(const at::Tensor& gy, const at::Tensor& x,
                             int pad) {
-  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
-  auto gyc = gy.contiguous();
-  auto xc = x.contiguous();
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat,
+              "wino_bwdw: x must be a 4-D fp32 GPU tensor");
+  wino_check_operand(gy, x, "wino_bwdw", "gy");
+  wino_check_pad(pad, true, "wino_bwdw");
   const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
   const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
+  TORCH_CHECK(gy.size(0) == B, "wino_bwdw: batch of gy ", gy.size(0),
+              " is not x's ", B);
   TORCH_CHECK(OH == H + 2 * pad - 2 && OW == W + 2 * pad - 2,
               "wino_bwdw geometry");
-  TORCH_CHECK(OH % 2 == 0 && OW % 2 == 0, "wino_bwdw: even output dims only");
+  TORCH_CHECK(OH > 0 && OW > 0 && OH % 2 == 0 && OW % 2 == 0,
+              "wino_bwdw: even output dims only");
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
   const WinoTiles g =
       wino_tiles(B, OH, OW, std::max(Ci, Co), "conv2d_wino_bwdw");
   auto stream = c10::hip::getCurrentHIPStream().stream();
@@ -825,7 +878,8 @@ static WinoFusedArgs wino_fused_args(int B, int Ci, int H, int W, int Co,
   a.OW = W + 2 * pad - 2;
   const WinoTiles g = wino_tiles(B, a.OH, a.OW, 0, who);
   TORCH_CHECK(Co % 32 == 0 && g.T % 32 == 0 && Ci % 8 == 0 && a.OH % 2 == 0 &&
-              a.OW % 2 == 0 && g.T > 0, who, " shape requirements");
+              a.OW % 2 == 0 && g.T > 0 && Co > 0 && Ci > 0, who,
+              " shape requirements");
   a.tH = g.tH; a.tW = g.tW; a.d_thw = g.d_thw; a.d_tw = g.d_tw;
   const WinoSplit sp = wino_fused_split(Co, Ci, g.T);
   a.ci_per = sp.per;
@@ -862,14 +916,19 @@ static WinoBwdwArgs wino_bwdw_args(int B, int Ci, int H, int W, int Co, int pad,
 
 at::Tensor conv2d_wino_bwdw_fused(const at::Tensor& gy, const at::Tensor& x,
                                   int pad) {
-  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && gy.dim() == 4 && x.dim() == 4);
-  auto gyc = gy.contiguous();
-  auto xc = x.contiguous();
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat,
+              "wino_bwdw_fused: x must be a 4-D fp32 GPU tensor");
+  wino_check_operand(gy, x, "wino_bwdw_fused", "gy");
+  wino_check_pad(pad, true, "wino_bwdw_fused");
+  TORCH_CHECK(gy.size(0) == x.size(0), "wino_bwdw_fused: batch of gy ",
+              gy.size(0), " is not x's ", x.size(0));
   const int Co = gy.size(1), Ci = x.size(1);
   WinoBwdwArgs a = wino_bwdw_args(x.size(0), Ci, x.size(2), x.size(3), Co, pad,
                                   "wino_bwdw_fused");
-  TORCH_CHECK(gy.size(2) == a.OH && gy.size(3) == a.OW,
+  TORCH_CHECK(gy.size(2) == a.OH && gy.size(3) == a.OW && a.OH > 0 && a.OW > 0,
               "wino_bwdw_fused geometry");
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   auto slab = at::empty({a.nz, Co, Ci, 3, 3}, x.options());
@@ -893,17 +952,20 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
                              c10::optional<at::Tensor> bias, int pad,
                              bool flip) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kFloat);
+  wino_check_operand(w, x, "wino_fused", "w");
   TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, "wino_fused: 3x3 only");
-  auto xc = x.contiguous();
-  auto wc = w.contiguous();
+  wino_check_pad(pad, flip, "wino_fused");
   const int B = x.size(0);
   const int Co = flip ? w.size(1) : w.size(0);
   const int Ci = flip ? w.size(0) : w.size(1);
   TORCH_CHECK(x.size(1) == Ci, "wino_fused: channel mismatch");
+  const float* bias_p = wino_bias_ptr(bias, x, Co, "wino_fused");
   // the weight transform runs IN-KERNEL (one (co,ci) pair per thread per
   // staging step) — no wt launch, no 16*Co*Ci frequency tensor
   WinoFusedArgs a = wino_fused_args(B, Ci, x.size(2), x.size(3), Co, pad,
                                     (int)w.size(1), "wino_fused");
+  auto xc = x.contiguous();
+  auto wc = w.contiguous();
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   // every slice covers a non-empty ci range and T, Co are tile multiples, so
@@ -913,7 +975,7 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
   if (a.nz > 1) slab = at::empty({a.nz, B, Co, a.OH, a.OW}, x.options());
   a.x = xc.data_ptr<float>();
   a.w = wc.data_ptr<float>();
-  a.bias = bias.has_value() ? bias->data_ptr<float>() : nullptr;
+  a.bias = bias_p;
   a.y = a.nz > 1 ? slab.data_ptr<float>() : y.data_ptr<float>();
   wino_dispatch_flip(flip, [&](auto F) {
     hipLaunchKernelGGL(wino_fused_kernel<decltype(F)::value>,
@@ -924,6 +986,15 @@ at::Tensor conv2d_wino_fused(const at::Tensor& x, const at::Tensor& w,
                 stream);
   }
   return y;
+}
+
+// (ci slices, ci per slice) of wino_fused_kernel for Co output and Ci reduction
+// channels over T tiles: what conv2d_wino_fused uses in either direction
+std::tuple<int, int> conv2d_wino_fused_splits(int Co, int Ci, int T) {
+  TORCH_CHECK(Co > 0 && Co % 32 == 0 && T > 0 && T % 32 == 0 && Ci > 0 &&
+              Ci % 8 == 0, "wino_fused_splits shape requirements");
+  const WinoSplit sp = wino_fused_split(Co, Ci, T);
+  return {sp.splits, sp.per};
 }
 
 // (bwd-data ci slices, ci per slice, bwd-weight tile slices, tiles per slice)
@@ -946,12 +1017,11 @@ std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor& gy,
                                                    const at::Tensor& x,
                                                    const at::Tensor& w, int pad,
                                                    int interleave) {
-  TORCH_CHECK(gy.is_cuda() && x.is_cuda() && w.is_cuda() && gy.dim() == 4 &&
-              x.dim() == 4 && w.dim() == 4 && gy.scalar_type() == at::kFloat);
+  TORCH_CHECK(gy.is_cuda() && gy.dim() == 4 && gy.scalar_type() == at::kFloat);
+  wino_check_operand(x, gy, "bwd_pair", "x");
+  wino_check_operand(w, gy, "bwd_pair", "w");
   TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, "bwd_pair: 3x3 only");
-  auto gyc = gy.contiguous();
-  auto xc = x.contiguous();
-  auto wc = w.contiguous();
+  wino_check_pad(pad, true, "bwd_pair");
   const int B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
   const int Co = gy.size(1), OH = gy.size(2), OW = gy.size(3);
   TORCH_CHECK(gy.size(0) == B && w.size(0) == Co && w.size(1) == Ci &&
@@ -959,6 +1029,9 @@ std::tuple<at::Tensor, at::Tensor> conv2d_bwd_pair(const at::Tensor& gy,
               "bwd_pair geometry");
   WinoFusedArgs d = wino_bwd_data_args(B, Ci, H, W, Co, pad, "bwd_pair");
   WinoBwdwArgs g = wino_bwdw_args(B, Ci, H, W, Co, pad, "bwd_pair");
+  auto gyc = gy.contiguous();
+  auto xc = x.contiguous();
+  auto wc = w.contiguous();
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   auto gx = at::empty({B, Ci, H, W}, x.options());

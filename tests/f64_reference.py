@@ -4,8 +4,10 @@ Each function is the textbook formula in torch double, a few lines, with no
 call into the package under test and no call to the torch op it stands for
 (tests/test_f64_reference.py checks each against that torch op in double).
 Inputs are fp32 test inputs; every function upcasts what it is given.
-tests/test_small_kernels_f64_gpu.py and tests/test_gemm_conv_f64_gpu.py
-compare the HIP kernels with these.
+tests/test_small_kernels_f64_gpu.py, tests/test_gemm_conv_f64_gpu.py and
+tests/test_wino_f64_gpu.py compare the HIP kernels with these.  The Winograd
+functions at the end take a dtype: they are the conv again, by the kernels'
+algorithm.
 """
 
 import math
@@ -257,6 +259,78 @@ def conv2d_bwd_weight(gy, x, KH, KW, stride, pad):
 
 def conv2d_bwd_bias(gy):
     return _d(gy).sum(dim=(0, 2, 3))
+
+
+# ---------------- Winograd F(2x2, 3x3) ----------------
+# The 3x3 stride-1 conv as the Winograd kernels compute it, from the three
+# matrices in the header of csrc/wino_math.h, in the dtype asked for: float64
+# to tie the algebra to conv2d above, float32 as the comparison implementation
+# of the tolerance rule (the same algorithm as the kernels, in plain torch).
+# Tile (th, tw) owns output pixels (2 th.., 2 tw..) and reads the 4x4 patch of
+# the zero-padded input whose corner is (2 th, 2 tw).  The _abs forms apply
+# |B^T|, |G|, |A| to |x|, |w|, |gy|: the sum of the magnitudes of every term
+# an output is made of, which bounds what rounding can do to it.
+
+WINO_BT = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
+WINO_G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]]
+WINO_A = [[1, 0], [1, 1], [1, -1], [0, -1]]
+
+
+def _wino_operands(dtype, absolute, *tensors):
+    """(B^T, G, A) and the tensors, on the CPU in dtype; |.| of all if asked"""
+    ts = [torch.tensor(m, dtype=dtype) for m in (WINO_BT, WINO_G, WINO_A)]
+    ts += [None if t is None else t.detach().to(device="cpu", dtype=dtype)
+           for t in tensors]
+    return [t.abs() if absolute and t is not None else t for t in ts]
+
+
+def _wino_V(x, pad, Bt):
+    """B^T d B of every tile's patch: [B, Ci, tH, tW, 4, 4]"""
+    B, C, H, W = x.shape
+    assert (H + 2 * pad) % 2 == 0 and (W + 2 * pad) % 2 == 0, "even outputs only"
+    xp = torch.zeros(B, C, H + 2 * pad, W + 2 * pad, dtype=x.dtype)
+    xp[:, :, pad:pad + H, pad:pad + W] = x
+    d = xp.unfold(2, 4, 2).unfold(3, 4, 2)
+    return torch.einsum("ij,bcthjk,lk->bcthil", Bt, d, Bt)
+
+
+def _wino_conv2d(x, w, bias, pad, dtype, absolute):
+    Bt, G, A, x, w, bias = _wino_operands(dtype, absolute, x, w, bias)
+    V = _wino_V(x, pad, Bt)
+    U = torch.einsum("ij,ocjk,lk->ocil", G, w, G)             # G g G^T
+    M = torch.einsum("ocil,bcthil->bothil", U, V)
+    Y = torch.einsum("ji,bothjk,kl->bothil", A, M, A)         # A^T M A
+    y = Y.permute(0, 1, 2, 4, 3, 5).reshape(x.shape[0], w.shape[0],
+                                            2 * Y.shape[2], 2 * Y.shape[3])
+    return y if bias is None else y + _chan(bias)
+
+
+def _wino_conv2d_bwd_weight(gy, x, pad, dtype, absolute):
+    Bt, G, A, gy, x = _wino_operands(dtype, absolute, gy, x)
+    V = _wino_V(x, pad, Bt)
+    assert gy.shape[2:] == (2 * V.shape[2], 2 * V.shape[3]), "geometry"
+    g = gy.unfold(2, 2, 2).unfold(3, 2, 2)                    # [B, Co, tH, tW, 2, 2]
+    Wg = torch.einsum("ij,bothjk,lk->bothil", A, g, A)        # A gy A^T
+    dU = torch.einsum("bothil,bcthil->ocil", Wg, V)
+    return torch.einsum("ji,ocjk,kl->ocil", G, dU, G)         # G^T dU G
+
+
+def wino_conv2d(x, w, bias=None, pad=1, dtype=torch.float64):
+    """y = A^T [ (G g G^T) .* (B^T d B) ] A, summed over Ci, per 2x2 tile"""
+    return _wino_conv2d(x, w, bias, pad, dtype, False)
+
+
+def wino_conv2d_abs(x, w, bias=None, pad=1, dtype=torch.float64):
+    return _wino_conv2d(x, w, bias, pad, dtype, True)
+
+
+def wino_conv2d_bwd_weight(gy, x, pad=1, dtype=torch.float64):
+    """gw = G^T [ (A gy A^T) .* (B^T d B) ] G, summed over the tiles"""
+    return _wino_conv2d_bwd_weight(gy, x, pad, dtype, False)
+
+
+def wino_conv2d_bwd_weight_abs(gy, x, pad=1, dtype=torch.float64):
+    return _wino_conv2d_bwd_weight(gy, x, pad, dtype, True)
 
 
 # ---------------- embedding ----------------

@@ -1,8 +1,10 @@
-"""The float64 yardstick of tests/test_small_kernels_f64_gpu.py and
-tests/test_gemm_conv_f64_gpu.py, checked on the
-CPU against torch's own double-precision ops.  Both sides are float64, so
-they agree to a few ulps of double; 1e-12 relative to the largest value leaves
-room for a different summation order and nothing else."""
+"""The float64 yardstick of tests/test_small_kernels_f64_gpu.py,
+tests/test_gemm_conv_f64_gpu.py and tests/test_wino_f64_gpu.py, checked on the
+CPU against torch's own double-precision ops (the Winograd forms against the
+tap-by-tap conv of the same module, which is checked against torch's).  Both
+sides are float64, so they agree to a few ulps of double; 1e-12 relative to
+the largest value leaves room for a different summation order and nothing
+else."""
 
 import pytest
 import torch
@@ -225,3 +227,58 @@ def test_conv2d(case):
     _same(R.conv2d_bwd_data(gy, w, s, p, H, W), xd.grad, "conv2d gx")
     _same(R.conv2d_bwd_weight(gy, x, KH, KW, s, p), wd.grad, "conv2d gw")
     _same(R.conv2d_bwd_bias(gy), bd.grad, "conv2d gb")
+
+
+# (B, Ci, H, W, Co, pad): even outputs, H != W, a tile of padding alone (pad 3)
+WINO_REF_CASES = [(2, 3, 6, 4, 4, 0), (2, 3, 4, 6, 5, 1), (1, 5, 2, 6, 3, 2),
+                  (2, 2, 4, 2, 3, 3), (1, 1, 2, 2, 1, 1), (3, 17, 10, 6, 7, 1)]
+
+
+def _wino_inputs(case, integers):
+    B, Ci, H, W, Co, pad = case
+    g = _gen(12)
+    shapes = ((B, Ci, H, W), (Co, Ci, 3, 3), (Co,),
+              (B, Co, H + 2 * pad - 2, W + 2 * pad - 2))
+    if integers:
+        return [torch.randint(-4, 5, s, generator=g).float() for s in shapes]
+    return [torch.randn(s, generator=g) for s in shapes]
+
+
+@pytest.mark.parametrize("case", WINO_REF_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_wino_in_double_is_the_conv(case):
+    """the Winograd algebra in double against the tap-by-tap definition"""
+    pad = case[5]
+    x, w, b, gy = _wino_inputs(case, False)
+    _same(R.wino_conv2d(x, w, b, pad), R.conv2d(x, w, b, 1, pad), "wino fwd")
+    _same(R.wino_conv2d(x, w, None, pad), R.conv2d(x, w, None, 1, pad),
+          "wino fwd, no bias")
+    _same(R.wino_conv2d_bwd_weight(gy, x, pad),
+          R.conv2d_bwd_weight(gy, x, 3, 3, 1, pad), "wino gw")
+    if pad <= 2:
+        # bwd-data: the same conv of gy with the rotated, transposed weight
+        wf = w.flip(2, 3).transpose(0, 1)
+        _same(R.wino_conv2d(gy, wf, None, 2 - pad),
+              R.conv2d_bwd_data(gy, w, 1, pad, case[2], case[3]), "wino gx")
+    # the |.| forms bound the plain ones and equal them on positive operands
+    xa, wa, ba, ga = (t.abs() for t in (x, w, b, gy))
+    for plain, absf in ((R.wino_conv2d(x, w, b, pad), R.wino_conv2d_abs(x, w, b, pad)),
+                        (R.wino_conv2d_bwd_weight(gy, x, pad),
+                         R.wino_conv2d_bwd_weight_abs(gy, x, pad))):
+        assert bool((plain.abs() <= absf * (1 + 1e-12)).all())
+    assert bool((R.wino_conv2d_abs(x, w, b, pad) >=
+                 R.conv2d(xa, wa, ba, 1, pad) * (1 - 1e-12)).all())
+    assert bool((R.wino_conv2d_bwd_weight_abs(gy, x, pad) >=
+                 R.conv2d_bwd_weight(ga, xa, 3, 3, 1, pad) * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("case", WINO_REF_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_wino_in_float32_is_exact_on_integers(case):
+    """integers from [-4, 4]: every intermediate has at most two fractional
+    bits and stays far below 2^22, so fp32 loses nothing"""
+    pad = case[5]
+    x, w, b, gy = _wino_inputs(case, True)
+    y = R.wino_conv2d(x, w, b, pad, torch.float32)
+    gw = R.wino_conv2d_bwd_weight(gy, x, pad, torch.float32)
+    assert y.dtype == gw.dtype == torch.float32
+    assert torch.equal(y.double(), R.conv2d(x, w, b, 1, pad))
+    assert torch.equal(gw.double(), R.conv2d_bwd_weight(gy, x, 3, 3, 1, pad))

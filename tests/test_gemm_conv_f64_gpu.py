@@ -79,7 +79,7 @@ import torch
 import torch.nn.functional as F
 
 import f64_reference as R
-from f64_compare import EPS32, cmp, cpu64, exact
+from f64_compare import _ceiling, _draw, _gen, cmp, exact
 
 pytestmark = pytest.mark.gpu
 
@@ -91,31 +91,6 @@ NAN, INF = float("nan"), float("inf")
 def _native():
     from split_learning_amd.ops import native
     return native()
-
-
-def _gen(seed):
-    return torch.Generator(device="cpu").manual_seed(seed)
-
-
-def _draw(kind, shape, g):
-    """exact: integers from [-4, 4]; randn: standard normal"""
-    if kind == "exact":
-        return torch.randint(-4, 5, shape, generator=g).float()
-    return torch.randn(shape, generator=g)
-
-
-def _ceiling(family, what, kernel, ref64, abs64, terms):
-    """|kernel - ref| <= (terms + 1) * 2^-23 * sum |a||b|, element by element"""
-    k, r, lim = cpu64(kernel), cpu64(ref64), (terms + 1) * EPS32 * cpu64(abs64)
-    fin = torch.isfinite(r)
-    err = (k - r).abs()[fin]
-    lim = lim[fin]
-    pos = lim > 0
-    share = float((err[pos] / lim[pos]).max()) if bool(pos.any()) else 0.0
-    print(f"CEIL | {family} | {what} | terms {terms} | share {share:.3e}")
-    assert bool((err <= lim).all()), (
-        f"{family} {what}: {int((err > lim).sum())} elements past the fma-chain "
-        f"ceiling, worst share {share:.3e}")
 
 
 # ---------------- GEMM ----------------
