@@ -27,9 +27,18 @@ SOURCES = [
     "elementwise.hip",
     "loss.hip",
     "attention.hip",
+    "attention_tiled.hip",
     "optim.hip",
     "bindings.cpp",
 ]
+
+# per-source device flags.  attention_tiled.hip: no packed-fp32 instructions
+# (v_pk_mul_f32 and kin) for its float4 accumulator rescales; scalar fp32 ops
+# only, like its MFMA math.
+EXTRA_FLAGS = {
+    "attention_tiled.hip": ["-Xclang", "-target-feature",
+                            "-Xclang", "-packed-fp32-ops"],
+}
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -96,7 +105,7 @@ def build(verbose: bool = True, force: bool = False) -> str:
         if (not force and os.path.exists(op)
                 and all(os.path.getmtime(op) >= os.path.getmtime(d) for d in deps)):
             continue
-        cmd = [hipcc, "-c", sp, "-o", op] + cxxflags
+        cmd = [hipcc, "-c", sp, "-o", op] + cxxflags + EXTRA_FLAGS.get(src, [])
         if src.endswith(".cpp"):
             cmd.append("-x")
             cmd.append("c++")  # host-only TU

@@ -25,7 +25,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
-#include "common.h"
+#include "torch_util.h"
 
 namespace slk {
 
@@ -130,19 +130,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       out[base + (long)r * hd + lane] = acc;
     }
   }
-}
-
-// key_bias is [BH/heads, S] additive fp32 (BERT feeds -10000 at pads, MHA
-// -inf); one row per sample, shared by that sample's heads.
-static at::Tensor check_key_bias(const at::Tensor& kb, long BH, long S,
-                                 int64_t heads, const char* who) {
-  TORCH_CHECK(heads >= 1 && BH % heads == 0, who, ": BH=", BH,
-              " is not a multiple of heads=", heads);
-  TORCH_CHECK(kb.is_cuda() && kb.scalar_type() == at::kFloat && kb.dim() == 2 &&
-                  kb.size(0) == BH / heads && kb.size(1) == S,
-              who, ": key_bias must be a float32 cuda tensor [BH/heads=",
-              BH / heads, ", S=", S, "]");
-  return kb.contiguous();
 }
 
 // ---------------------------------------------------------------------------

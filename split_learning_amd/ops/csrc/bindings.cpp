@@ -90,6 +90,17 @@ std::vector<at::Tensor> attn_softmax_fwd(const at::Tensor&,
                                          c10::optional<at::Tensor>);
 at::Tensor attn_softmax_bwd(const at::Tensor&, const at::Tensor&,
                             c10::optional<at::Tensor>, double, double);
+// attention_tiled.hip
+std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, double, double, int64_t,
+                                       c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>, int64_t);
+std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       double, double, int64_t,
+                                       c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>, int64_t);
 // loss.hip
 at::Tensor softmax_fwd(const at::Tensor&);
 at::Tensor softmax_bwd(const at::Tensor&, const at::Tensor&);
@@ -196,6 +207,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("offset") = py::none());
   m.def("attn_softmax_bwd", &slk::attn_softmax_bwd, py::arg("g_dropped"),
         py::arg("probs"), py::arg("mask"), py::arg("scale"), py::arg("p") = 0.0);
+  m.def("attn_tiled_fwd", &slk::attn_tiled_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
+        py::arg("heads") = 1);
+  m.def("attn_tiled_bwd", &slk::attn_tiled_bwd, py::arg("gout"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"),
+        py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
+        py::arg("heads") = 1);
   m.def("softmax_fwd", &slk::softmax_fwd);
   m.def("softmax_bwd", &slk::softmax_bwd);
   m.def("ce_fwd", &slk::ce_fwd);

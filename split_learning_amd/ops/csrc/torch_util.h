@@ -46,6 +46,20 @@ static inline int reduce_chunks(long per_channel) {
   return (int)c;
 }
 
+// key_bias is [BH/heads, S] additive fp32 (BERT feeds -10000 at pads, MHA
+// -inf); one row per sample, shared by that sample's heads.  (attention.hip,
+// attention_tiled.hip)
+static inline at::Tensor check_key_bias(const at::Tensor& kb, long BH, long S,
+                                        int64_t heads, const char* who) {
+  TORCH_CHECK(heads >= 1 && BH % heads == 0, who, ": BH=", BH,
+              " is not a multiple of heads=", heads);
+  TORCH_CHECK(kb.is_cuda() && kb.scalar_type() == at::kFloat && kb.dim() == 2 &&
+                  kb.size(0) == BH / heads && kb.size(1) == S,
+              who, ": key_bias must be a float32 cuda tensor [BH/heads=",
+              BH / heads, ", S=", S, "]");
+  return kb.contiguous();
+}
+
 // out[i] = sum_s slab[s*numel + i], s in fixed order (conv2d.hip)
 void slab_reduce(const float* slab, int splits, float* out, long numel,
                  hipStream_t stream);

@@ -550,6 +550,56 @@ def attention(q, k, v, scale, dropout_p=0.0, training=False, key_bias=None,
                         p, seed, offset_t, _key_bias_arg(key_bias), int(heads))
 
 
+class AttnTiledFn(Function):
+    """Tiled MFMA attention (attention_tiled.hip): one forward launch with an
+    online softmax, two backward launches that recompute the probabilities
+    from lse and redraw the dropout mask from the offset the forward read.
+    Saves q, k, v, out, lse [BH,S] and that one-element offset tensor (plus
+    the [B,S] bias): nothing of size S^2."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, p, seed, offset_t, key_bias=None,
+                heads=1):
+        out, lse, used = native().attn_tiled_fwd(q, k, v, scale, p, seed,
+                                                 offset_t, key_bias, heads)
+        ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
+        ctx.args = (scale, float(p), seed, heads)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        q, k, v, out, lse, used, key_bias = ctx.saved_tensors
+        scale, p, seed, heads = ctx.args
+        gq, gk, gv = native().attn_tiled_bwd(gy, q, k, v, out, lse, scale, p,
+                                             seed, used, key_bias, heads)
+        return gq, gk, gv, None, None, None, None, None, None
+
+
+def attn_tiled_ok(q, k, v) -> bool:
+    """tiled path precondition: three [BH, S, hd in {32, 64}] fp32 CUDA
+    tensors of one shape; any S >= 1."""
+    return (q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
+            and q.shape[2] in (32, 64) and q.shape[1] >= 1
+            and k.shape == q.shape and v.shape == q.shape
+            and k.dtype == q.dtype and v.dtype == q.dtype)
+
+
+def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
+                    key_bias=None, heads=1):
+    """attention() on the tiled kernels: same arguments, same dropout counter
+    and keep decisions, any S."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0:
+        counter = _counter_for(q.device)
+        counter.add_(1)
+        seed, offset_t = _DROPOUT_STATE["seed"], counter
+    else:
+        seed, offset_t = 0, None
+    return AttnTiledFn.apply(q.contiguous(), k.contiguous(), v.contiguous(),
+                             float(scale), p, seed, offset_t,
+                             _key_bias_arg(key_bias), int(heads))
+
+
 class AttnProbsFn(Function):
     """dropout(softmax(scores * scale + key_bias)) in ONE kernel per direction
     (attention.hip attn_softmax_fwd / attn_softmax_bwd): the masked GEMM

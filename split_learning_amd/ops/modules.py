@@ -253,6 +253,20 @@ def _fused_attn_worth_it(bh, s_len, dropout_p, training) -> bool:
     return _FATTN_FORCE
 
 
+# Tiled MFMA attention (attention_tiled.hip): the default from S = 129 up, the
+# shapes the one-launch kernel cannot take and where the chain keeps S^2 state
+# and computes in the platform BLAS; SLK_FATTN=tiled routes every S to it
+# (profiles/SUMMARY.md "Tiled attention" has the measurements behind both).
+_FATTN_TILED = os.environ.get("SLK_FATTN", "0") == "tiled"
+_TILED_MIN_S = 129
+
+
+def _tiled_attn_route(q, k, v) -> bool:
+    return (_use_native("attn", q) and "fattn" not in _DBG_TORCH
+            and hf.attn_tiled_ok(q, k, v)
+            and (q.shape[1] >= _TILED_MIN_S or _FATTN_TILED))
+
+
 def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
                    scale: Optional[float] = None, key_bias=None,
                    heads: int = 1):
@@ -266,6 +280,9 @@ def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
     if key_bias is not None:
         return _attention_core_biased(q, k, v, dropout_p, training, s,
                                       key_bias, heads)
+    if _tiled_attn_route(q, k, v):
+        return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
+                                  training=training)
     if (_use_native("attn", q) and "fattn" not in _DBG_TORCH and q.dim() == 3
             and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
             and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
@@ -293,6 +310,10 @@ def _attention_core_biased(q, k, v, dropout_p, training, s, key_bias, heads):
         raise ValueError(
             f"key_bias must be [B*H / heads, S] for q {tuple(q.shape)} and "
             f"heads={heads}, got {tuple(key_bias.shape)}")
+    if _tiled_attn_route(q, k, v):
+        return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
+                                  training=training, key_bias=key_bias,
+                                  heads=heads)
     if (_use_native("attn", q) and "fattn" not in _DBG_TORCH
             and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
             and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
