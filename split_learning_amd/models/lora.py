@@ -10,12 +10,18 @@ state dict is shipped to the server, so .pth files contain plain weights.
 from __future__ import annotations
 
 import math
+import os
 from typing import Iterable
 
 import torch
 import torch.nn as nn
 
-from ..ops.modules import HipDropout
+from ..ops.modules import _DBG_TORCH, HipDropout
+
+# SLK_LORA=chain keeps the unfused adapter chain on CUDA too (A/B measurement;
+# profiles/SUMMARY.md "Fused LoRA adapter")
+_LORA_CHAIN = (os.environ.get("SLK_LORA", "") == "chain"
+               or bool(_DBG_TORCH & {"linear", "dropout"}))
 
 
 class LoRALinear(nn.Module):
@@ -32,6 +38,13 @@ class LoRALinear(nn.Module):
         nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
 
     def forward(self, x):
+        if x.is_cuda and not _LORA_CHAIN:
+            from ..ops import functional as hf
+            if hf.lora_ok(x, self.base.weight, self.lora_A, self.lora_B):
+                return hf.lora_linear(x, self.base.weight, self.base.bias,
+                                      self.lora_A, self.lora_B, self.scaling,
+                                      self.lora_dropout.p, self.training)
+        # the chain: CPU, shapes lora_ok turns away, and SLK_LORA=chain
         y = self.base(x)
         xd = self.lora_dropout(x)
         if x.is_cuda:

@@ -101,6 +101,16 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor&, const at::Tensor&,
                                        double, double, int64_t,
                                        c10::optional<at::Tensor>,
                                        c10::optional<at::Tensor>, int64_t);
+// lora.hip
+std::vector<at::Tensor> lora_fwd(at::Tensor, const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, double, double, int64_t,
+                                 c10::optional<at::Tensor>);
+std::vector<at::Tensor> lora_bwd(const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, c10::optional<at::Tensor>,
+                                 double, double, int64_t,
+                                 c10::optional<at::Tensor>);
+int lora_wgrad_slabs(int64_t, int64_t, int64_t);
 // loss.hip
 at::Tensor softmax_fwd(const at::Tensor&);
 at::Tensor softmax_bwd(const at::Tensor&, const at::Tensor&);
@@ -216,6 +226,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
         py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
         py::arg("heads") = 1);
+  m.def("lora_fwd", &slk::lora_fwd, py::arg("y"), py::arg("x"),
+        py::arg("lora_A"), py::arg("lora_B"), py::arg("scaling"),
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = py::none());
+  m.def("lora_bwd", &slk::lora_bwd, py::arg("g"), py::arg("x"),
+        py::arg("lora_A"), py::arg("lora_B"), py::arg("xa"), py::arg("gx"),
+        py::arg("scaling"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = py::none());
+  m.def("lora_wgrad_slabs", &slk::lora_wgrad_slabs, py::arg("M"), py::arg("K"),
+        py::arg("N"));
   m.def("softmax_fwd", &slk::softmax_fwd);
   m.def("softmax_bwd", &slk::softmax_bwd);
   m.def("ce_fwd", &slk::ce_fwd);

@@ -402,6 +402,83 @@ def dropout(x, p, training=True):
 
 
 # ---------------------------------------------------------------------------
+# LoRA linear (lora.hip): base GEMM + fused adapter
+# ---------------------------------------------------------------------------
+
+class LoraLinearFn(Function):
+    """out = x W^T + b + scaling * (dropout(x) A^T) B^T.  The base product and
+    g @ W keep the route linear() gives them (platform BLAS above
+    _LIB_LIN_THRESH, the MFMA GEMM below); everything else is one launch
+    forward (lora_fwd, in place on the base output) and three backward
+    (lora_bwd: rows, weight gradients, slab sum).  Saves x, W, A, B, xa [M,r]
+    and the one-element offset the forward read: no xd, mask or delta."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, lora_A, lora_B, scaling, p, seed, offset_t):
+        xs = x.reshape(-1, x.shape[-1]).contiguous()
+        lib = 2.0 * xs.shape[0] * weight.shape[0] * weight.shape[1] >= _LIB_LIN_THRESH
+        if lib:
+            y = _F.linear(xs, weight, bias)
+        else:
+            y = native().linear_fwd(xs, weight, bias)
+        lora_A, lora_B = lora_A.contiguous(), lora_B.contiguous()
+        xa, used = native().lora_fwd(y, xs, lora_A, lora_B, scaling, p, seed,
+                                     offset_t)
+        ctx.save_for_backward(xs, weight, lora_A, lora_B, xa, used)
+        ctx.args = (scaling, p, seed, lib, bias is not None, x.shape)
+        return y.reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, weight, lora_A, lora_B, xa, used = ctx.saved_tensors
+        scaling, p, seed, lib, has_bias, x_shape = ctx.args
+        gys = gy.reshape(-1, gy.shape[-1]).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.matmul(gys, weight) if lib else _matmul_raw(gys, weight)
+        gA, gB = native().lora_bwd(gys, xs, lora_A, lora_B, xa, gx, scaling, p,
+                                   seed, used)
+        if ctx.needs_input_grad[1]:
+            gw = (torch.matmul(gys.t(), xs) if lib
+                  else _matmul_raw(gys, xs, trans_a=True))
+        if has_bias and ctx.needs_input_grad[2]:
+            gb = gys.sum(0) if lib else native().colsum_f32(gys)
+        if gx is not None:
+            gx = gx.reshape(x_shape)
+        return gx, gw, gb, gA, gB, None, None, None, None
+
+
+def lora_ok(x, weight, lora_A, lora_B) -> bool:
+    """fused adapter precondition: fp32 CUDA tensors, x [..., K], W [N,K],
+    A [r,K], B [N,r], 1 <= r <= 16, K % 4 == 0, N % 4 == 0."""
+    ts = (x, weight, lora_A, lora_B)
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if x.dim() < 1 or weight.dim() != 2 or lora_A.dim() != 2 or lora_B.dim() != 2:
+        return False
+    n, k = weight.shape
+    r = lora_A.shape[0]
+    return (1 <= r <= 16 and k % 4 == 0 and n % 4 == 0 and x.shape[-1] == k
+            and lora_A.shape[1] == k and tuple(lora_B.shape) == (n, r)
+            and x.data_ptr() % 16 == 0)
+
+
+def lora_linear(x, weight, bias, lora_A, lora_B, scaling, dropout_p=0.0,
+                training=False):
+    """Linear with a LoRA adapter on the fused kernels; dropout(x) draws from
+    dropout()'s stream: same counter, same keep decisions."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0:
+        counter = _counter_for(x.device)
+        counter.add_(1)
+        seed, offset_t = _DROPOUT_STATE["seed"], counter
+    else:
+        seed, offset_t = 0, None
+    return LoraLinearFn.apply(x, weight, bias, lora_A, lora_B, float(scaling),
+                              p, seed, offset_t)
+
+
+# ---------------------------------------------------------------------------
 # LayerNorm
 # ---------------------------------------------------------------------------
 
