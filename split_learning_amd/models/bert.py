@@ -14,11 +14,15 @@ attention_core (MFMA batched GEMM + fused softmax on GPU).
 
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn as nn
 
 from ..ops.modules import (HipDropout, HipEmbedding, HipGELU, HipLayerNorm,
-                           HipLinear, HipTanh, attention_core)
+                           HipLinear, HipTanh, _heads_attn_route,
+                           attention_core)
+from ..ops import functional as hf
 from .partitioned import PartitionedModel
 
 
@@ -75,9 +79,20 @@ class BertSdpaSelfAttention(nn.Module):
     def forward(self, hidden_states, attention_mask=None):
         B, S, E = hidden_states.shape
         H, hd = self.num_attention_heads, self.attention_head_size
-        q = self.query(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
-        k = self.key(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
-        v = self.value(hidden_states).view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
+        q, k, v = (self.query(hidden_states), self.key(hidden_states),
+                   self.value(hidden_states))
+        if q.dim() == 3 and _heads_attn_route(q, k, v, H):
+            # tiled kernels on the projections' [B,S,E] layout: no head
+            # permutes; same additive mask as below
+            key_bias = None if attention_mask is None else \
+                (1.0 - attention_mask.to(torch.float32)) * -10000.0
+            return hf.attention_heads(q, k, v, H, 1.0 / math.sqrt(hd),
+                                      dropout_p=self.dropout.p,
+                                      training=self.training,
+                                      key_bias=key_bias)
+        q = q.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
+        k = k.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
+        v = v.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         if attention_mask is None:
             ctx = attention_core(q, k, v, dropout_p=self.dropout.p, training=self.training)
         else:

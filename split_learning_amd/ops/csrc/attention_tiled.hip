@@ -36,6 +36,24 @@
 //   dV^T += gO^T P_d and dK^T += Q^T dS read gO and Q relabelled.
 //   Deterministic: no atomics, no zero-fill, each output written once.
 //
+// Two operand layouts, one kernel body (template parameter HEADS):
+//   contiguous   [BH,S,HD]: block bh reads ptr + bh*S*HD, rows HD apart.
+//   head-strided [B,S,H*HD] views, as a projection GEMM writes them: element
+//     (b, s, h, d) of an operand is ptr + b*batch + s*row + h*HD + d with the
+//     operand's own (batch, row) strides, bh = b*heads + h.  q, k, v may be
+//     three tensors or the column thirds of one packed [B,S,3E] (row = 3E);
+//     out and gout are [B,S,E] as the output projection reads and writes
+//     them; for packed operands gq, gk, gv are the thirds of ONE [B,S,3E]
+//     gradient (dq kernel: columns [0,E), dkv kernel: [E,3E)), so each
+//     element is still written exactly once and nothing is zero-filled or
+//     concatenated.  lse and delta stay [BH,S] and the dropout element index
+//     stays (bh*S + row)*S + key: only addresses differ, every MFMA, softmax
+//     update and LDS access is the contiguous kernel's, results bit for bit.
+//   b and h are block-uniform, so each operand's slice base is scalar
+//   arithmetic done once (at_slice); the row stride is one more SGPR.  The
+//   float4 moves need 16-byte-aligned bases and strides that are multiples
+//   of 4 floats; the host checks that (at_heads_operand).
+//
 // LDS layout.  Every staged tile [64][HD] is read in two patterns by the 32
 // lanes that share an LDS cycle (g in {0,1} or {2,3}; 32 banks of 4 bytes):
 //   (a) row 16j + c, column C + g          (16 rows x 2 adjacent columns)
@@ -54,7 +72,8 @@
 // Compiler resource report (hipcc --offload-arch=gfx950 -O3
 // -Rpass-analysis=kernel-resource-usage), the DROPOUT and BIAS instantiation
 // of each kernel (the most VGPRs of its four; the others reach the same
-// occupancy, the HD=32 dq kernel 3 waves); scratch is 0 in all 24:
+// occupancy, the HD=32 dq kernel 3 waves); scratch is 0 in all 24 contiguous
+// instantiations:
 //   kernel                      HD  VGPR  AGPR  LDS bytes  scratch  waves/SIMD
 //   attn_tiled_fwd_kernel       32   104    16      16640        0      4
 //   attn_tiled_fwd_kernel       64   174    16      33024        0      2
@@ -62,6 +81,9 @@
 //   attn_tiled_bwd_dq_kernel    64   195    40      33024        0      2
 //   attn_tiled_bwd_dkv_kernel   32   162    32      16896        0      2
 //   attn_tiled_bwd_dkv_kernel   64   244    48      33280        0      1
+// The 24 head-strided instantiations (HEADS = true) report the same VGPR,
+// AGPR, LDS and occupancy figures as their contiguous twins, row for row, and
+// scratch 0; the contiguous ones are unchanged by the template parameter.
 // The compiler spends registers on hoisted LDS addresses and batched LDS
 // reads; occupancy is register-bound, not LDS-bound (160 KB per CU).
 #include <type_traits>
@@ -99,6 +121,31 @@ __device__ __forceinline__ uint32_t at_rng_stream(uint64_t seed, uint64_t offset
   return (uint32_t)(slk_mix64(seed ^ slk_mix64(offset)) >> 32);  // = attn_fwd_kernel
 }
 
+// One operand's strides in floats (head-strided layout only).
+struct AtStride {
+  long batch;
+  int row;
+};
+
+// One block's [S][HD] slice of an operand: its first element and the distance
+// between rows.  Contiguous [BH,S,HD]: the distance is the constant HD and
+// folds into the address arithmetic as before.  Head-strided: b and h are
+// block-uniform, so the slice base is scalar arithmetic done once per operand.
+template <class T>
+struct AtSlice {
+  T* p;
+  int ld;
+};
+
+template <int HD, bool HEADS, class T>
+__device__ __forceinline__ AtSlice<T> at_slice(T* p, const AtStride& st, int bh,
+                                               int heads, int S) {
+  if constexpr (HEADS)
+    return {p + (long)(bh / heads) * st.batch + (bh % heads) * HD, st.row};
+  else
+    return {p + (long)bh * S * HD, HD};
+}
+
 // One [64][HD] tile on its way global -> registers -> LDS.  A thread moves
 // HD/16 float4s; rows >= S arrive as zeros (loaded from the clamped last row
 // and selected away: no load sits under a branch).
@@ -106,14 +153,14 @@ template <int HD>
 struct AtTile {
   static constexpr int NV = HD / 16;
   f32x4 r[NV];
-  __device__ __forceinline__ void load(const float* __restrict__ src, int row0,
+  __device__ __forceinline__ void load(AtSlice<const float> src, int row0,
                                        int S, int tid) {
     #pragma unroll
     for (int u = 0; u < NV; ++u) {
       const int i = tid + 256 * u;
       const int row = row0 + i / (HD / 4);
       const f32x4 x = *reinterpret_cast<const f32x4*>(
-          src + (long)min(row, S - 1) * HD + 4 * (i % (HD / 4)));
+          src.p + (long)min(row, S - 1) * src.ld + 4 * (i % (HD / 4)));
       r[u] = row < S ? x : f32x4{};
     }
   }
@@ -131,9 +178,9 @@ struct AtTile {
 // a wave's 16 rows as the B operand: lane (c, g) holds row c, columns 4*step+g
 template <int HD>
 __device__ __forceinline__ void at_load_rows(float (&reg)[HD / 4],
-                                             const float* __restrict__ src,
+                                             AtSlice<const float> src,
                                              int row, int S, int g) {
-  const float* p = src + (long)min(row, S - 1) * HD + g;
+  const float* p = src.p + (long)min(row, S - 1) * src.ld + g;
   #pragma unroll
   for (int s = 0; s < HD / 4; ++s) reg[s] = row < S ? p[4 * s] : 0.f;
 }
@@ -188,6 +235,8 @@ struct AtArgs {
   uint64_t seed;
   int S, heads;
   float scale, p, inv_keep;
+  // head-strided instantiations only (the contiguous ones never read them)
+  AtStride sq, sk, sv, so, sgo, sgq, sgk, sgv;
 };
 
 // the walked tile's additive row: bias (or 0) at keys < S, -inf past S
@@ -198,7 +247,7 @@ __device__ __forceinline__ float at_key_bias(const float* __restrict__ kbr,
   return BIAS ? kbr[key] : 0.f;
 }
 
-template <int HD, bool DROPOUT, bool BIAS>
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
 __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsK[AT_TILE * HD];
   __shared__ __align__(16) float ldsV[AT_TILE * HD];
@@ -207,8 +256,10 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int S = a.S, bh = blockIdx.y;
-  const long base = (long)bh * S * HD;
   const int row = blockIdx.x * AT_TILE + 16 * wid + c;
+  const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
+  const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
+  const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
 
   uint32_t rng_stream = 0;
   if (DROPOUT) {
@@ -219,7 +270,7 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   const float* kbr = BIAS ? a.key_bias + (long)(bh / a.heads) * S : nullptr;
 
   float qreg[HD / 4];
-  at_load_rows<HD>(qreg, a.q + base, row, S, g);
+  at_load_rows<HD>(qreg, qs, row, S, g);
 
   f32x4 oacc[HD / 16] = {};
   float m = -INFINITY, l = 0.f;   // l: this lane's share of the row sum
@@ -228,8 +279,8 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   AtTile<HD> tk, tv;
   float nb = 0.f;
   const int ntiles = (S + AT_TILE - 1) / AT_TILE;
-  tk.load(a.k + base, 0, S, tid);
-  tv.load(a.v + base, 0, S, tid);
+  tk.load(ks, 0, S, tid);
+  tv.load(vs, 0, S, tid);
   if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, tid, S);
 
   for (int t = 0; t < ntiles; ++t) {
@@ -239,8 +290,8 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
     if (tid < AT_TILE) ldsB[tid] = nb;
     __syncthreads();
     if (t + 1 < ntiles) {
-      tk.load(a.k + base, (t + 1) * AT_TILE, S, tid);
-      tv.load(a.v + base, (t + 1) * AT_TILE, S, tid);
+      tk.load(ks, (t + 1) * AT_TILE, S, tid);
+      tv.load(vs, (t + 1) * AT_TILE, S, tid);
       if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, (t + 1) * AT_TILE + tid, S);
     }
 
@@ -289,7 +340,8 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   l = at_group_sum(l);
   if (row < S) {
     const float inv = 1.f / l;    // no finite key: 0/0 = NaN, as torch
-    float* o = a.out + base + (long)row * HD + 4 * g;
+    const auto os = at_slice<HD, HEADS>(a.out, a.so, bh, a.heads, S);
+    float* o = os.p + (long)row * os.ld + 4 * g;
     #pragma unroll
     for (int db = 0; db < HD / 16; ++db)
       *reinterpret_cast<f32x4*>(o + 16 * db) = oacc[db] * inv;
@@ -297,7 +349,7 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   }
 }
 
-template <int HD, bool DROPOUT, bool BIAS>
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
 __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsK[AT_TILE * HD];
   __shared__ __align__(16) float ldsV[AT_TILE * HD];
@@ -306,8 +358,11 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int S = a.S, bh = blockIdx.y;
-  const long base = (long)bh * S * HD;
   const int row = blockIdx.x * AT_TILE + 16 * wid + c;
+  const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
+  const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
+  const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
+  const auto gouts = at_slice<HD, HEADS>(a.gout, a.sgo, bh, a.heads, S);
 
   uint32_t rng_stream = 0;
   if (DROPOUT)
@@ -315,13 +370,15 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   const float* kbr = BIAS ? a.key_bias + (long)(bh / a.heads) * S : nullptr;
 
   float qreg[HD / 4], greg[HD / 4];
-  at_load_rows<HD>(qreg, a.q + base, row, S, g);
-  at_load_rows<HD>(greg, a.gout + base, row, S, g);
+  at_load_rows<HD>(qreg, qs, row, S, g);
+  at_load_rows<HD>(greg, gouts, row, S, g);
   // delta = sum_d gO * O (= sum_c dP*P, with or without dropout: O = P_d V)
   float delta = 0.f;
   {
     float oreg[HD / 4];
-    at_load_rows<HD>(oreg, a.out + base, row, S, g);
+    at_load_rows<HD>(
+        oreg, at_slice<HD, HEADS, const float>(a.out, a.so, bh, a.heads, S),
+        row, S, g);
     #pragma unroll
     for (int s = 0; s < HD / 4; ++s) delta += greg[s] * oreg[s];
     delta = at_group_sum(delta);
@@ -336,8 +393,8 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   AtTile<HD> tk, tv;
   float nb = 0.f;
   const int ntiles = (S + AT_TILE - 1) / AT_TILE;
-  tk.load(a.k + base, 0, S, tid);
-  tv.load(a.v + base, 0, S, tid);
+  tk.load(ks, 0, S, tid);
+  tv.load(vs, 0, S, tid);
   if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, tid, S);
 
   for (int t = 0; t < ntiles; ++t) {
@@ -347,8 +404,8 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
     if (tid < AT_TILE) ldsB[tid] = nb;
     __syncthreads();
     if (t + 1 < ntiles) {
-      tk.load(a.k + base, (t + 1) * AT_TILE, S, tid);
-      tv.load(a.v + base, (t + 1) * AT_TILE, S, tid);
+      tk.load(ks, (t + 1) * AT_TILE, S, tid);
+      tv.load(vs, (t + 1) * AT_TILE, S, tid);
       if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, (t + 1) * AT_TILE + tid, S);
     }
 
@@ -378,14 +435,15 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   }
 
   if (row < S) {
-    float* o = a.gq + base + (long)row * HD + 4 * g;
+    const auto gqs = at_slice<HD, HEADS>(a.gq, a.sgq, bh, a.heads, S);
+    float* o = gqs.p + (long)row * gqs.ld + 4 * g;
     #pragma unroll
     for (int db = 0; db < HD / 16; ++db)
       *reinterpret_cast<f32x4*>(o + 16 * db) = dq[db] * a.scale;
   }
 }
 
-template <int HD, bool DROPOUT, bool BIAS>
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
 __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsQ[AT_TILE * HD];
   __shared__ __align__(16) float ldsG[AT_TILE * HD];
@@ -395,8 +453,11 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int S = a.S, bh = blockIdx.y;
-  const long base = (long)bh * S * HD;
   const int key = blockIdx.x * AT_TILE + 16 * wid + c;
+  const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
+  const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
+  const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
+  const auto gouts = at_slice<HD, HEADS>(a.gout, a.sgo, bh, a.heads, S);
 
   uint32_t rng_stream = 0;
   if (DROPOUT)
@@ -405,8 +466,8 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
   const float kb = at_key_bias<BIAS>(kbr, key, S);   // -inf: a key past S
 
   float kreg[HD / 4], vreg[HD / 4];
-  at_load_rows<HD>(kreg, a.k + base, key, S, g);
-  at_load_rows<HD>(vreg, a.v + base, key, S, g);
+  at_load_rows<HD>(kreg, ks, key, S, g);
+  at_load_rows<HD>(vreg, vs, key, S, g);
 
   f32x4 dk[HD / 16] = {}, dv[HD / 16] = {};
 
@@ -421,8 +482,8 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
 
   AtTile<HD> tq, tg;
   const int ntiles = (S + AT_TILE - 1) / AT_TILE;
-  tq.load(a.q + base, 0, S, tid);
-  tg.load(a.gout + base, 0, S, tid);
+  tq.load(qs, 0, S, tid);
+  tg.load(gouts, 0, S, tid);
   float ns = load_row_stat(0);
 
   for (int t = 0; t < ntiles; ++t) {
@@ -433,8 +494,8 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
     else if (tid < 2 * AT_TILE) ldsD[tid - AT_TILE] = ns;
     __syncthreads();
     if (t + 1 < ntiles) {
-      tq.load(a.q + base, (t + 1) * AT_TILE, S, tid);
-      tg.load(a.gout + base, (t + 1) * AT_TILE, S, tid);
+      tq.load(qs, (t + 1) * AT_TILE, S, tid);
+      tg.load(gouts, (t + 1) * AT_TILE, S, tid);
       ns = load_row_stat(t + 1);
     }
 
@@ -467,8 +528,10 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
   }
 
   if (key < S) {
-    float* ov = a.gv + base + (long)key * HD + 4 * g;
-    float* ok = a.gk + base + (long)key * HD + 4 * g;
+    const auto gvs = at_slice<HD, HEADS>(a.gv, a.sgv, bh, a.heads, S);
+    const auto gks = at_slice<HD, HEADS>(a.gk, a.sgk, bh, a.heads, S);
+    float* ov = gvs.p + (long)key * gvs.ld + 4 * g;
+    float* ok = gks.p + (long)key * gks.ld + 4 * g;
     #pragma unroll
     for (int db = 0; db < HD / 16; ++db) {
       *reinterpret_cast<f32x4*>(ov + 16 * db) = dv[db];
@@ -500,20 +563,19 @@ struct AtProblem {
   at::Tensor kb, off;
 };
 
-static AtProblem at_check(const at::Tensor& q, double p,
-                          const c10::optional<at::Tensor>& offset,
-                          const c10::optional<at::Tensor>& key_bias,
-                          int64_t heads, const char* who) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kFloat && q.dim() == 3, who,
-              ": q must be a float32 cuda tensor [BH,S,hd]");
+// the rules both layouts share, on the problem's (BH, S, hd)
+static AtProblem at_check_dims(const at::Tensor& q, long BH, long S, long hd,
+                               double p,
+                               const c10::optional<at::Tensor>& offset,
+                               const c10::optional<at::Tensor>& key_bias,
+                               int64_t heads, const char* who) {
   AtProblem pr;
-  pr.BH = q.size(0);
-  TORCH_CHECK(q.size(1) >= 1 && q.size(1) < (1 << 24), who, ": S=", q.size(1),
-              " out of range");
-  pr.S = (int)q.size(1);
-  pr.hd = (int)q.size(2);
+  pr.BH = BH;
+  TORCH_CHECK(S >= 1 && S < (1 << 24), who, ": S=", S, " out of range");
+  pr.S = (int)S;
+  pr.hd = (int)hd;
   TORCH_CHECK(pr.hd == 32 || pr.hd == 64, who, ": hd must be 32 or 64 (got ",
-              pr.hd, ")");
+              hd, ")");
   TORCH_CHECK(pr.BH <= 65535, who, ": BH=", pr.BH, " exceeds the grid's 65535");
   TORCH_CHECK(p >= 0.0 && p < 1.0, who, ": p in [0,1) (got ", p, ")");
   pr.drop = p > 0.0;
@@ -532,12 +594,22 @@ static AtProblem at_check(const at::Tensor& q, double p,
   return pr;
 }
 
-#define SLK_AT_DISPATCH(KERNEL, pr, grid, stream, args)                        \
+static AtProblem at_check(const at::Tensor& q, double p,
+                          const c10::optional<at::Tensor>& offset,
+                          const c10::optional<at::Tensor>& key_bias,
+                          int64_t heads, const char* who) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kFloat && q.dim() == 3, who,
+              ": q must be a float32 cuda tensor [BH,S,hd]");
+  return at_check_dims(q, q.size(0), q.size(1), q.size(2), p, offset, key_bias,
+                       heads, who);
+}
+
+#define SLK_AT_DISPATCH(KERNEL, HEADS, pr, grid, stream, args)                 \
   do {                                                                         \
     auto go = [&](auto hd_c, auto drop_c, auto bias_c) {                       \
       hipLaunchKernelGGL(                                                      \
           (KERNEL<decltype(hd_c)::value, decltype(drop_c)::value,              \
-                  decltype(bias_c)::value>),                                   \
+                  decltype(bias_c)::value, HEADS>),                            \
           grid, dim3(256), 0, stream, args);                                   \
     };                                                                         \
     auto go_b = [&](auto hd_c, auto drop_c) {                                  \
@@ -591,7 +663,7 @@ std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor& q, const at::Tensor& k,
   a.offset_out = pr.drop ? used.data_ptr<long>() : nullptr;
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_fwd_kernel, pr, grid, stream, a);
+  SLK_AT_DISPATCH(attn_tiled_fwd_kernel, false, pr, grid, stream, a);
   return {out, lse, used};
 }
 
@@ -629,10 +701,149 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor& gout, const at::Tensor&
   a.gv = gv.data_ptr<float>();
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, pr, grid, stream, a);
+  SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, false, pr, grid, stream, a);
   // same stream: delta is complete before the dkv kernel starts
-  SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, pr, grid, stream, a);
+  SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, false, pr, grid, stream, a);
   return {gq, gk, gv};
+}
+
+// ---------------------------------------------------------------------------
+// head-strided layout: operands are [B,S,E = heads*hd] views with a unit last
+// stride, read where the projection GEMM left them
+// ---------------------------------------------------------------------------
+
+// the float4 loads and stores need a 16-byte-aligned base and row and batch
+// strides that keep that alignment; a dimension of size 1 is never stepped
+static AtStride at_heads_operand(const at::Tensor& t, const at::Tensor& like,
+                                 const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.dim() == 3, who,
+              ": ", name, " must be a float32 cuda tensor [B,S,E]");
+  TORCH_CHECK(t.device() == like.device() && t.sizes() == like.sizes(), who,
+              ": ", name, " must have q's shape (B, S, E) and device");
+  TORCH_CHECK(t.stride(2) == 1, who, ": ", name,
+              " must have a last-dim stride of 1 (got ", t.stride(2), ")");
+  const long rs = t.size(1) > 1 ? t.stride(1) : 0;
+  const long bs = t.size(0) > 1 ? t.stride(0) : 0;
+  TORCH_CHECK(rs % 4 == 0 && bs % 4 == 0 && rs < (1L << 31), who, ": ", name,
+              "'s row and batch strides (", rs, ", ", bs,
+              ") must be multiples of 4 floats: the kernels move float4s");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, who, ": ",
+              name, " must start at a 16-byte-aligned address");
+  return {bs, (int)rs};
+}
+
+static AtProblem at_heads_check(const at::Tensor& q, int64_t heads, double p,
+                                const c10::optional<at::Tensor>& offset,
+                                const c10::optional<at::Tensor>& key_bias,
+                                const char* who) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kFloat && q.dim() == 3, who,
+              ": q must be a float32 cuda tensor [B,S,E]");
+  TORCH_CHECK(heads >= 1 && q.size(2) % heads == 0, who, ": E=", q.size(2),
+              " is not heads=", heads, " times a head size");
+  return at_check_dims(q, q.size(0) * heads, q.size(1), q.size(2) / heads, p,
+                       offset, key_bias, heads, who);
+}
+
+// q, k, v are the column slices [0,E), [E,2E), [2E,3E) of one dense [B,S,3E]
+static bool at_heads_packed(const at::Tensor& q, const at::Tensor& k,
+                            const at::Tensor& v) {
+  const long B = q.size(0), S = q.size(1), E = q.size(2);
+  return q.is_alias_of(k) && q.is_alias_of(v) && k.strides() == q.strides() &&
+         v.strides() == q.strides() &&
+         k.storage_offset() == q.storage_offset() + E &&
+         v.storage_offset() == q.storage_offset() + 2 * E &&
+         (S == 1 || q.stride(1) == 3 * E) && (B == 1 || q.stride(0) == S * 3 * E);
+}
+
+// -> {out [B,S,E], lse [B*heads,S], offset_used [1] int64 (empty when p == 0)}
+std::vector<at::Tensor> attn_heads_fwd(const at::Tensor& q, const at::Tensor& k,
+                                       const at::Tensor& v, int64_t heads,
+                                       double scale, double p, int64_t seed,
+                                       c10::optional<at::Tensor> offset,
+                                       c10::optional<at::Tensor> key_bias) {
+  const char* who = "attn_heads_fwd";
+  const AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  auto out = at::empty(q.sizes(), q.options());
+  auto lse = at::empty({pr.BH, pr.S}, q.options());
+  auto used = at::empty({pr.drop ? 1 : 0}, q.options().dtype(at::kLong));
+  AtArgs a = at_args(pr, q, k, v, scale, p, seed, heads);
+  a.sq = at_heads_operand(q, q, who, "q");
+  a.sk = at_heads_operand(k, q, who, "k");
+  a.sv = at_heads_operand(v, q, who, "v");
+  a.so = at_heads_operand(out, q, who, "out");
+  if (pr.BH == 0) return {out, lse, used};
+  a.out = out.data_ptr<float>();
+  a.lse = lse.data_ptr<float>();
+  a.offset_out = pr.drop ? used.data_ptr<long>() : nullptr;
+  const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  SLK_AT_DISPATCH(attn_tiled_fwd_kernel, true, pr, grid, stream, a);
+  return {out, lse, used};
+}
+
+// -> {gq, gk, gv} in q's layout class: for q, k, v packed in one [B,S,3E]
+// tensor, three views of ONE [B,S,3E] gradient, which is returned as a fourth
+// element (dq kernel writes columns [0,E), dkv kernel [E,3E): every element
+// once, nothing zero-filled or concatenated); otherwise three dense [B,S,E]
+std::vector<at::Tensor> attn_heads_bwd(const at::Tensor& gout, const at::Tensor& q,
+                                       const at::Tensor& k, const at::Tensor& v,
+                                       const at::Tensor& out, const at::Tensor& lse,
+                                       int64_t heads, double scale, double p,
+                                       int64_t seed,
+                                       c10::optional<at::Tensor> offset,
+                                       c10::optional<at::Tensor> key_bias) {
+  const char* who = "attn_heads_bwd";
+  if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
+  const AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  TORCH_CHECK(!pr.drop || pr.off.defined(), who,
+              ": p > 0 needs the offset tensor the forward returned");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.scalar_type() == at::kFloat && lse.dim() == 2 &&
+                  lse.size(0) == pr.BH && lse.size(1) == pr.S,
+              who, ": lse must be a float32 cuda tensor [B*heads,S]");
+  auto lc = lse.contiguous();
+  // the incoming gradient is autograd's, not the caller's: take any layout
+  // the kernels can read, copy the rest
+  TORCH_CHECK(gout.dim() == 3 && gout.sizes() == q.sizes(), who,
+              ": gout must have q's shape (B, S, E)");
+  const bool g_ok = gout.stride(2) == 1 && gout.stride(1) % 4 == 0 &&
+                    gout.stride(0) % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(gout.data_ptr()) & 15) == 0;
+  auto gc = g_ok ? gout : gout.contiguous();
+  const long B = q.size(0), E = q.size(2);
+  AtArgs a = at_args(pr, q, k, v, scale, p, seed, heads);
+  a.sq = at_heads_operand(q, q, who, "q");
+  a.sk = at_heads_operand(k, q, who, "k");
+  a.sv = at_heads_operand(v, q, who, "v");
+  a.so = at_heads_operand(out, q, who, "out");
+  a.sgo = at_heads_operand(gc, q, who, "gout");
+  std::vector<at::Tensor> g;
+  if (at_heads_packed(q, k, v)) {
+    auto packed = at::empty({B, pr.S, 3 * E}, q.options());
+    g = {packed.narrow(2, 0, E), packed.narrow(2, E, E),
+         packed.narrow(2, 2 * E, E), packed};
+  } else {
+    g = {at::empty(q.sizes(), q.options()), at::empty(q.sizes(), q.options()),
+         at::empty(q.sizes(), q.options())};
+  }
+  if (pr.BH == 0) return g;
+  a.sgq = at_heads_operand(g[0], q, who, "gq");
+  a.sgk = at_heads_operand(g[1], q, who, "gk");
+  a.sgv = at_heads_operand(g[2], q, who, "gv");
+  auto delta = at::empty_like(lc);
+  a.out = out.data_ptr<float>();
+  a.lse = lc.data_ptr<float>();
+  a.gout = gc.data_ptr<float>();
+  a.delta = delta.data_ptr<float>();
+  a.gq = g[0].data_ptr<float>();
+  a.gk = g[1].data_ptr<float>();
+  a.gv = g[2].data_ptr<float>();
+  const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, true, pr, grid, stream, a);
+  // same stream: delta is complete before the dkv kernel starts
+  SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, true, pr, grid, stream, a);
+  return g;
 }
 
 }  // namespace slk

@@ -101,6 +101,16 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor&, const at::Tensor&,
                                        double, double, int64_t,
                                        c10::optional<at::Tensor>,
                                        c10::optional<at::Tensor>, int64_t);
+std::vector<at::Tensor> attn_heads_fwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, int64_t, double, double,
+                                       int64_t, c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>);
+std::vector<at::Tensor> attn_heads_bwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       int64_t, double, double, int64_t,
+                                       c10::optional<at::Tensor>,
+                                       c10::optional<at::Tensor>);
 // lora.hip
 std::vector<at::Tensor> lora_fwd(at::Tensor, const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, double, double, int64_t,
@@ -226,6 +236,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
         py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
         py::arg("heads") = 1);
+  m.def("attn_heads_fwd", &slk::attn_heads_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("heads"), py::arg("scale"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("offset") = py::none(),
+        py::arg("key_bias") = py::none());
+  m.def("attn_heads_bwd", &slk::attn_heads_bwd, py::arg("gout"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"),
+        py::arg("heads"), py::arg("scale"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("offset") = py::none(),
+        py::arg("key_bias") = py::none());
   m.def("lora_fwd", &slk::lora_fwd, py::arg("y"), py::arg("x"),
         py::arg("lora_A"), py::arg("lora_B"), py::arg("scaling"),
         py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = py::none());

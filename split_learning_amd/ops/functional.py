@@ -677,6 +677,96 @@ def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
                              _key_bias_arg(key_bias), int(heads))
 
 
+class AttnHeadsFn(Function):
+    """The tiled kernels on the projections' own layout (attention_tiled.hip,
+    head-strided instantiations): q, k, v are [B,S,E] views with a unit last
+    stride, out is [B,S,E] dense, no permute copy on either side.
+
+    x is q, or, with k and v None, the dense [B,S,3E] tensor whose three
+    E-wide column slices are q, k, v: its gradient is then the one [B,S,3E]
+    buffer the backward kernels fill, and autograd has nothing to assemble.
+    Saves the operand views, out, lse [B*heads,S], the used-offset tensor and
+    the bias: nothing of size S^2."""
+
+    @staticmethod
+    def forward(ctx, x, k, v, heads, scale, p, seed, offset_t, key_bias=None):
+        ctx.packed = k is None
+        q, k, v = x.split(x.shape[-1] // 3, dim=-1) if ctx.packed else (x, k, v)
+        out, lse, used = native().attn_heads_fwd(q, k, v, heads, scale, p, seed,
+                                                 offset_t, key_bias)
+        ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
+        ctx.args = (heads, scale, float(p), seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        q, k, v, out, lse, used, key_bias = ctx.saved_tensors
+        heads, scale, p, seed = ctx.args
+        g = native().attn_heads_bwd(gy, q, k, v, out, lse, heads, scale, p,
+                                    seed, used, key_bias)
+        if ctx.packed:
+            return (g[3],) + (None,) * 8
+        return g[0], g[1], g[2], None, None, None, None, None, None
+
+
+def attn_heads_ok(q, k, v, heads) -> bool:
+    """attention_heads' precondition: three [B, S, E = heads * hd] fp32 CUDA
+    tensors of one shape, hd in {32, 64}, S >= 1, B * heads within the grid;
+    unit last stride, row and batch strides multiples of 4 floats and
+    16-byte-aligned bases (the kernels move float4s)."""
+    if not (q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
+            and heads >= 1 and q.shape[2] % heads == 0
+            and q.shape[2] // heads in (32, 64) and q.shape[1] >= 1
+            and q.shape[0] * heads <= 65535):
+        return False
+    return all(t.shape == q.shape and t.dtype == q.dtype
+               and t.device == q.device and t.stride(2) == 1
+               and (t.shape[1] == 1 or t.stride(1) % 4 == 0)
+               and (t.shape[0] == 1 or t.stride(0) % 4 == 0)
+               and t.data_ptr() % 16 == 0 for t in (q, k, v))
+
+
+def _packed_base(q, k, v, base):
+    """base (default: the tensor q is a view of) if it is a dense [B,S,3E]
+    tensor whose column thirds are exactly q, k, v; else None"""
+    base = q._base if base is None else base
+    B, S, E = q.shape
+    if (base is None or tuple(base.shape) != (B, S, 3 * E)
+            or base.dtype != q.dtype or not base.is_contiguous()):
+        return None
+    at = base.data_ptr()
+    step = E * q.element_size()
+    if ((q.data_ptr(), k.data_ptr(), v.data_ptr())
+            == (at, at + step, at + 2 * step)
+            and q.stride() == k.stride() == v.stride() == base.stride()):
+        return base
+    return None
+
+
+def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
+                    key_bias=None, packed=None):
+    """attention_tiled() without the head permutes: q, k, v [B,S,E] as the
+    projections wrote them (three tensors, or three column views of one packed
+    [B,S,3E]), result [B,S,E] as the output projection reads it.  Head h is
+    columns [h*hd, (h+1)*hd); key_bias is [B,S].  Same dropout counter and
+    keep decisions as attention_tiled on the permuted operands.
+
+    packed names the [B,S,3E] tensor q, k, v were split from, for a caller
+    whose q._base is not that tensor (a view of a view reports the root)."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0:
+        counter = _counter_for(q.device)
+        counter.add_(1)
+        seed, offset_t = _DROPOUT_STATE["seed"], counter
+    else:
+        seed, offset_t = 0, None
+    base = _packed_base(q, k, v, packed)
+    if base is not None:
+        q, k, v = base, None, None
+    return AttnHeadsFn.apply(q, k, v, int(heads), float(scale), p, seed,
+                             offset_t, _key_bias_arg(key_bias))
+
+
 class AttnProbsFn(Function):
     """dropout(softmax(scores * scale + key_bias)) in ONE kernel per direction
     (attention.hip attn_softmax_fwd / attn_softmax_bwd): the masked GEMM

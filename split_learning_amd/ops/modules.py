@@ -168,7 +168,14 @@ class HipMultiheadAttention(nn.MultiheadAttention):
         qkv = hf.linear(x, self.in_proj_weight, self.in_proj_bias)  # [B,S,3E]
         q, k, v = qkv.split(E, dim=-1)
         scale = 1.0 / math.sqrt(hd)
-        if S <= 128 and hd <= 64 and (hd & (hd - 1)) == 0 \
+        if _heads_attn_route(q, k, v, H):
+            # tiled kernels on qkv's own layout: the three column views go in
+            # as they are, the context comes out as out_proj reads it
+            ctxv = hf.attention_heads(q, k, v, H, scale,
+                                      dropout_p=self.dropout,
+                                      training=self.training,
+                                      key_bias=key_bias, packed=qkv)
+        elif S <= 128 and hd <= 64 and (hd & (hd - 1)) == 0 \
                 and "fattn" not in _DBG_TORCH \
                 and _fused_attn_worth_it(B * H, S, self.dropout, self.training):
             q = q.reshape(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd)
@@ -264,6 +271,14 @@ _TILED_MIN_S = 129
 def _tiled_attn_route(q, k, v) -> bool:
     return (_use_native("attn", q) and "fattn" not in _DBG_TORCH
             and hf.attn_tiled_ok(q, k, v)
+            and (q.shape[1] >= _TILED_MIN_S or _FATTN_TILED))
+
+
+def _heads_attn_route(q, k, v, heads) -> bool:
+    """the tiled route's rule for callers that hold [B,S,E] projections:
+    hf.attention_heads reads them in place (no permute copies)"""
+    return (_use_native("attn", q) and "fattn" not in _DBG_TORCH
+            and hf.attn_heads_ok(q, k, v, heads)
             and (q.shape[1] >= _TILED_MIN_S or _FATTN_TILED))
 
 
