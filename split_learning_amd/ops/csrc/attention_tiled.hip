@@ -1,6 +1,6 @@
 // Tiled MFMA attention for gfx950: flash-style forward with an online softmax
 // and a two-kernel recompute backward.  Any S >= 1, hd in {32, 64}, optional
-// additive key bias and in-kernel dropout; no [BH,S,S] array exists anywhere:
+// additive key bias, causal mask and in-kernel dropout; no [BH,S,S] array exists anywhere:
 // the forward saves out and lse = m + log(l) ([BH,S]), the backward recomputes
 // P = exp(score*scale + bias - lse) and redraws the keep mask from the offset
 // the forward read (returned as a one-element device tensor, so a hipGraph
@@ -54,6 +54,28 @@
 //   float4 moves need 16-byte-aligned bases and strides that are multiples
 //   of 4 floats; the host checks that (at_heads_operand).
 //
+// Causal mode (template parameter CAUSAL; query row attends to keys <= row).
+// Row tile and walked tile are both 64, so a (query tile, key tile) pair is
+// fully visible (key tile < query tile), empty (key tile > query tile) or the
+// diagonal.  Empty pairs are never visited: the forward and dq kernels walk
+// key tiles 0..qt (prologue load, prefetch and loop bound), the dkv kernel
+// walks query tiles kt..last (ldsL / ldsD staging starts there too).  Fully
+// visible tiles run the non-causal body.  On the diagonal tile the mask is a
+// select on registers, by tile-local position: forward and dq lanes hold
+// query row 16*wid + c against keys 16j + 4g + r, the dkv lane holds key
+// 16*wid + c against query rows 16i + 4g + r; an entry with key > row gets
+// the score -inf before the running max (forward) or the exponent -inf (dq,
+// dkv).  Its probability is then exp(-inf) = +0 exactly, and every product it
+// enters (P V, dS K, P_d gO, dS Q; the operands are finite) is an exact zero
+// added to an accumulator, the same zero a skipped tile leaves out: a key in
+// a row's future cannot move a bit of that row's output, and gets no gradient
+// from it.  No mask tensor is read and nothing is added to LDS.  Key bias and
+// dropout combine unchanged: the dropout element index stays
+// (bh*S + row)*S + key, so the keep decisions are the non-causal kernels'.
+// Blocks carry unequal work (qt + 1 resp. ntiles - kt tiles) and take their
+// (tile, bh) from the launch order level by level, heaviest level first
+// (at_block); the non-causal mapping is blockIdx as before.
+//
 // LDS layout.  Every staged tile [64][HD] is read in two patterns by the 32
 // lanes that share an LDS cycle (g in {0,1} or {2,3}; 32 banks of 4 bytes):
 //   (a) row 16j + c, column C + g          (16 rows x 2 adjacent columns)
@@ -84,6 +106,16 @@
 // The 24 head-strided instantiations (HEADS = true) report the same VGPR,
 // AGPR, LDS and occupancy figures as their contiguous twins, row for row, and
 // scratch 0; the contiguous ones are unchanged by the template parameter.
+// The 48 causal instantiations (same command, DROPOUT and BIAS, contiguous;
+// scratch 0 in all 48, the head-strided twins within 3 VGPRs and at the same
+// occupancy); the 48 non-causal ones are unchanged by the template parameter:
+//   kernel                      HD  VGPR  AGPR  LDS bytes  scratch  waves/SIMD
+//   attn_tiled_fwd_kernel       32   112    16      16640        0      4
+//   attn_tiled_fwd_kernel       64   178    16      33024        0      2
+//   attn_tiled_bwd_dq_kernel    32   118    40      16640        0      3
+//   attn_tiled_bwd_dq_kernel    64   200    32      33024        0      2
+//   attn_tiled_bwd_dkv_kernel   32   134    44      16896        0      2
+//   attn_tiled_bwd_dkv_kernel   64   232    48      33280        0      1
 // The compiler spends registers on hoisted LDS addresses and batched LDS
 // reads; occupancy is register-bound, not LDS-bound (160 KB per CU).
 #include <type_traits>
@@ -247,7 +279,33 @@ __device__ __forceinline__ float at_key_bias(const float* __restrict__ kbr,
   return BIAS ? kbr[key] : 0.f;
 }
 
-template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
+// Which (tile, bh) a block takes; the grid is (tiles, BH) in both modes.
+// Non-causal: the block indices as they are.  Causal: a forward / dq block of
+// query tile qt walks qt + 1 key tiles and a dkv block of key tile kt walks
+// tiles - kt query tiles, so the blocks are taken in launch order level by
+// level: all bh of the heaviest tile first (heavy_last: that is the last
+// tile, else tile 0), then all bh of the next.  Neighbours in launch order
+// then carry equal work, whatever rule spreads them over the chip, and the
+// light blocks fill the tail.  (Tile-fastest orders put every bh's heavy
+// tile on the same launch-order residue: profiles/SUMMARY.md.)
+struct AtBlock {
+  int tile, bh;
+};
+template <bool CAUSAL>
+__device__ __forceinline__ AtBlock at_block(bool heavy_last) {
+  if (!CAUSAL) return {(int)blockIdx.x, (int)blockIdx.y};
+  const unsigned long id = (unsigned long)blockIdx.y * gridDim.x + blockIdx.x;
+  const int level = (int)(id / gridDim.y);
+  return {heavy_last ? (int)gridDim.x - 1 - level : level, (int)(id % gridDim.y)};
+}
+
+// Causal mode, diagonal tile (query tile == key tile): tile-local key `key`
+// is hidden from tile-local query row `row` when it lies in the row's future.
+__device__ __forceinline__ bool at_hidden(bool diagonal, int row, int key) {
+  return diagonal && key > row;
+}
+
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsK[AT_TILE * HD];
   __shared__ __align__(16) float ldsV[AT_TILE * HD];
@@ -255,8 +313,9 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int S = a.S, bh = blockIdx.y;
-  const int row = blockIdx.x * AT_TILE + 16 * wid + c;
+  const AtBlock blk = at_block<CAUSAL>(true);
+  const int S = a.S, bh = blk.bh, qt = blk.tile;
+  const int row = qt * AT_TILE + 16 * wid + c;
   const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
   const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
   const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
@@ -278,7 +337,7 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
 
   AtTile<HD> tk, tv;
   float nb = 0.f;
-  const int ntiles = (S + AT_TILE - 1) / AT_TILE;
+  const int ntiles = CAUSAL ? qt + 1 : (S + AT_TILE - 1) / AT_TILE;
   tk.load(ks, 0, S, tid);
   tv.load(vs, 0, S, tid);
   if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, tid, S);
@@ -306,6 +365,8 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         w[j][r] = sacc[j][r] * a.scale + kb[r];
+        if (CAUSAL && at_hidden(t == qt, 16 * wid + c, 16 * j + 4 * g + r))
+          w[j][r] = -INFINITY;
         mx = fmaxf(mx, w[j][r]);
       }
     }
@@ -349,7 +410,7 @@ __global__ __launch_bounds__(256) void attn_tiled_fwd_kernel(AtArgs a) {
   }
 }
 
-template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsK[AT_TILE * HD];
   __shared__ __align__(16) float ldsV[AT_TILE * HD];
@@ -357,8 +418,9 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int S = a.S, bh = blockIdx.y;
-  const int row = blockIdx.x * AT_TILE + 16 * wid + c;
+  const AtBlock blk = at_block<CAUSAL>(true);
+  const int S = a.S, bh = blk.bh, qt = blk.tile;
+  const int row = qt * AT_TILE + 16 * wid + c;
   const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
   const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
   const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
@@ -392,7 +454,7 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
 
   AtTile<HD> tk, tv;
   float nb = 0.f;
-  const int ntiles = (S + AT_TILE - 1) / AT_TILE;
+  const int ntiles = CAUSAL ? qt + 1 : (S + AT_TILE - 1) / AT_TILE;
   tk.load(ks, 0, S, tid);
   tv.load(vs, 0, S, tid);
   if (tid < AT_TILE) nb = at_key_bias<BIAS>(kbr, tid, S);
@@ -420,7 +482,10 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         // keys past S: bias -inf -> P = 0, and dP = 0 from the zero-filled V
-        const float pr = expf(sacc[j][r] * a.scale + kb[r] - lse);
+        float x = sacc[j][r] * a.scale + kb[r] - lse;
+        if (CAUSAL && at_hidden(t == qt, 16 * wid + c, 16 * j + 4 * g + r))
+          x = -INFINITY;
+        const float pr = expf(x);
         float d = dp[j][r];
         if (DROPOUT) {
           const int key = t * AT_TILE + 16 * j + 4 * g + r;
@@ -443,7 +508,7 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dq_kernel(AtArgs a) {
   }
 }
 
-template <int HD, bool DROPOUT, bool BIAS, bool HEADS>
+template <int HD, bool DROPOUT, bool BIAS, bool HEADS, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
   __shared__ __align__(16) float ldsQ[AT_TILE * HD];
   __shared__ __align__(16) float ldsG[AT_TILE * HD];
@@ -452,8 +517,9 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int S = a.S, bh = blockIdx.y;
-  const int key = blockIdx.x * AT_TILE + 16 * wid + c;
+  const AtBlock blk = at_block<CAUSAL>(false);
+  const int S = a.S, bh = blk.bh, kt = blk.tile;
+  const int key = kt * AT_TILE + 16 * wid + c;
   const auto qs = at_slice<HD, HEADS>(a.q, a.sq, bh, a.heads, S);
   const auto ks = at_slice<HD, HEADS>(a.k, a.sk, bh, a.heads, S);
   const auto vs = at_slice<HD, HEADS>(a.v, a.sv, bh, a.heads, S);
@@ -482,11 +548,12 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
 
   AtTile<HD> tq, tg;
   const int ntiles = (S + AT_TILE - 1) / AT_TILE;
-  tq.load(qs, 0, S, tid);
-  tg.load(gouts, 0, S, tid);
-  float ns = load_row_stat(0);
+  const int t0 = CAUSAL ? kt : 0;   // query tiles above the diagonal see no key here
+  tq.load(qs, t0 * AT_TILE, S, tid);
+  tg.load(gouts, t0 * AT_TILE, S, tid);
+  float ns = load_row_stat(t0);
 
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = t0; t < ntiles; ++t) {
     __syncthreads();
     tq.store(ldsQ, tid);
     tg.store(ldsG, tid);
@@ -510,7 +577,10 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(AtArgs a) {
       const f32x4 D = *reinterpret_cast<const f32x4*>(&ldsD[16 * i + 4 * g]);
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pr = expf(sacc[i][r] * a.scale + kb - L[r]);
+        float x = sacc[i][r] * a.scale + kb - L[r];
+        if (CAUSAL && at_hidden(t == kt, 16 * i + 4 * g + r, 16 * wid + c))
+          x = -INFINITY;
+        const float pr = expf(x);
         float d = dp[i][r], pk = pr;
         if (DROPOUT) {
           const int row = t * AT_TILE + 16 * i + 4 * g + r;
@@ -559,7 +629,7 @@ static at::Tensor at_operand(const at::Tensor& t, const at::Tensor& like,
 struct AtProblem {
   long BH;
   int S, hd;
-  bool drop, bias;
+  bool drop, bias, causal;
   at::Tensor kb, off;
 };
 
@@ -570,6 +640,7 @@ static AtProblem at_check_dims(const at::Tensor& q, long BH, long S, long hd,
                                const c10::optional<at::Tensor>& key_bias,
                                int64_t heads, const char* who) {
   AtProblem pr;
+  pr.causal = false;
   pr.BH = BH;
   TORCH_CHECK(S >= 1 && S < (1 << 24), who, ": S=", S, " out of range");
   pr.S = (int)S;
@@ -606,15 +677,20 @@ static AtProblem at_check(const at::Tensor& q, double p,
 
 #define SLK_AT_DISPATCH(KERNEL, HEADS, pr, grid, stream, args)                 \
   do {                                                                         \
-    auto go = [&](auto hd_c, auto drop_c, auto bias_c) {                       \
+    auto go = [&](auto hd_c, auto drop_c, auto bias_c, auto causal_c) {        \
       hipLaunchKernelGGL(                                                      \
           (KERNEL<decltype(hd_c)::value, decltype(drop_c)::value,              \
-                  decltype(bias_c)::value, HEADS>),                            \
+                  decltype(bias_c)::value, HEADS,                              \
+                  decltype(causal_c)::value>),                                 \
           grid, dim3(256), 0, stream, args);                                   \
     };                                                                         \
+    auto go_c = [&](auto hd_c, auto drop_c, auto bias_c) {                     \
+      if ((pr).causal) go(hd_c, drop_c, bias_c, std::true_type{});             \
+      else go(hd_c, drop_c, bias_c, std::false_type{});                        \
+    };                                                                         \
     auto go_b = [&](auto hd_c, auto drop_c) {                                  \
-      if ((pr).bias) go(hd_c, drop_c, std::true_type{});                       \
-      else go(hd_c, drop_c, std::false_type{});                                \
+      if ((pr).bias) go_c(hd_c, drop_c, std::true_type{});                     \
+      else go_c(hd_c, drop_c, std::false_type{});                              \
     };                                                                         \
     auto go_d = [&](auto hd_c) {                                               \
       if ((pr).drop) go_b(hd_c, std::true_type{});                             \
@@ -648,9 +724,10 @@ std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor& q, const at::Tensor& k,
                                        double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       int64_t heads) {
+                                       int64_t heads, bool is_causal) {
   const char* who = "attn_tiled_fwd";
-  const AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
+  AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
+  pr.causal = is_causal;
   auto qc = at_operand(q, q, who, "q"), kc = at_operand(k, q, who, "k"),
        vc = at_operand(v, q, who, "v");
   auto out = at::empty_like(qc);
@@ -674,10 +751,11 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor& gout, const at::Tensor&
                                        double scale, double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       int64_t heads) {
+                                       int64_t heads, bool is_causal) {
   const char* who = "attn_tiled_bwd";
   if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
-  const AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
+  AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
+  pr.causal = is_causal;
   TORCH_CHECK(!pr.drop || pr.off.defined(), who,
               ": p > 0 needs the offset tensor the forward returned");
   auto qc = at_operand(q, q, who, "q"), kc = at_operand(k, q, who, "k"),
@@ -760,9 +838,11 @@ std::vector<at::Tensor> attn_heads_fwd(const at::Tensor& q, const at::Tensor& k,
                                        const at::Tensor& v, int64_t heads,
                                        double scale, double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
-                                       c10::optional<at::Tensor> key_bias) {
+                                       c10::optional<at::Tensor> key_bias,
+                                       bool is_causal) {
   const char* who = "attn_heads_fwd";
-  const AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  pr.causal = is_causal;
   auto out = at::empty(q.sizes(), q.options());
   auto lse = at::empty({pr.BH, pr.S}, q.options());
   auto used = at::empty({pr.drop ? 1 : 0}, q.options().dtype(at::kLong));
@@ -791,10 +871,12 @@ std::vector<at::Tensor> attn_heads_bwd(const at::Tensor& gout, const at::Tensor&
                                        int64_t heads, double scale, double p,
                                        int64_t seed,
                                        c10::optional<at::Tensor> offset,
-                                       c10::optional<at::Tensor> key_bias) {
+                                       c10::optional<at::Tensor> key_bias,
+                                       bool is_causal) {
   const char* who = "attn_heads_bwd";
   if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
-  const AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
+  pr.causal = is_causal;
   TORCH_CHECK(!pr.drop || pr.off.defined(), who,
               ": p > 0 needs the offset tensor the forward returned");
   TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&

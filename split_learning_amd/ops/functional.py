@@ -636,20 +636,22 @@ class AttnTiledFn(Function):
 
     @staticmethod
     def forward(ctx, q, k, v, scale, p, seed, offset_t, key_bias=None,
-                heads=1):
+                heads=1, is_causal=False):
         out, lse, used = native().attn_tiled_fwd(q, k, v, scale, p, seed,
-                                                 offset_t, key_bias, heads)
+                                                 offset_t, key_bias, heads,
+                                                 is_causal)
         ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
-        ctx.args = (scale, float(p), seed, heads)
+        ctx.args = (scale, float(p), seed, heads, is_causal)
         return out
 
     @staticmethod
     def backward(ctx, gy):
         q, k, v, out, lse, used, key_bias = ctx.saved_tensors
-        scale, p, seed, heads = ctx.args
+        scale, p, seed, heads, is_causal = ctx.args
         gq, gk, gv = native().attn_tiled_bwd(gy, q, k, v, out, lse, scale, p,
-                                             seed, used, key_bias, heads)
-        return gq, gk, gv, None, None, None, None, None, None
+                                             seed, used, key_bias, heads,
+                                             is_causal)
+        return gq, gk, gv, None, None, None, None, None, None, None
 
 
 def attn_tiled_ok(q, k, v) -> bool:
@@ -662,9 +664,10 @@ def attn_tiled_ok(q, k, v) -> bool:
 
 
 def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
-                    key_bias=None, heads=1):
+                    key_bias=None, heads=1, is_causal=False):
     """attention() on the tiled kernels: same arguments, same dropout counter
-    and keep decisions, any S."""
+    and keep decisions, any S.  is_causal: query row i attends to keys <= i
+    (the kernels skip the key tiles above the diagonal; no mask tensor)."""
     p = float(dropout_p) if training else 0.0
     if p > 0.0:
         counter = _counter_for(q.device)
@@ -674,7 +677,8 @@ def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
         seed, offset_t = 0, None
     return AttnTiledFn.apply(q.contiguous(), k.contiguous(), v.contiguous(),
                              float(scale), p, seed, offset_t,
-                             _key_bias_arg(key_bias), int(heads))
+                             _key_bias_arg(key_bias), int(heads),
+                             bool(is_causal))
 
 
 class AttnHeadsFn(Function):
@@ -689,24 +693,25 @@ class AttnHeadsFn(Function):
     the bias: nothing of size S^2."""
 
     @staticmethod
-    def forward(ctx, x, k, v, heads, scale, p, seed, offset_t, key_bias=None):
+    def forward(ctx, x, k, v, heads, scale, p, seed, offset_t, key_bias=None,
+                is_causal=False):
         ctx.packed = k is None
         q, k, v = x.split(x.shape[-1] // 3, dim=-1) if ctx.packed else (x, k, v)
         out, lse, used = native().attn_heads_fwd(q, k, v, heads, scale, p, seed,
-                                                 offset_t, key_bias)
+                                                 offset_t, key_bias, is_causal)
         ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
-        ctx.args = (heads, scale, float(p), seed)
+        ctx.args = (heads, scale, float(p), seed, is_causal)
         return out
 
     @staticmethod
     def backward(ctx, gy):
         q, k, v, out, lse, used, key_bias = ctx.saved_tensors
-        heads, scale, p, seed = ctx.args
+        heads, scale, p, seed, is_causal = ctx.args
         g = native().attn_heads_bwd(gy, q, k, v, out, lse, heads, scale, p,
-                                    seed, used, key_bias)
+                                    seed, used, key_bias, is_causal)
         if ctx.packed:
-            return (g[3],) + (None,) * 8
-        return g[0], g[1], g[2], None, None, None, None, None, None
+            return (g[3],) + (None,) * 9
+        return g[0], g[1], g[2], None, None, None, None, None, None, None
 
 
 def attn_heads_ok(q, k, v, heads) -> bool:
@@ -744,12 +749,13 @@ def _packed_base(q, k, v, base):
 
 
 def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
-                    key_bias=None, packed=None):
+                    key_bias=None, packed=None, is_causal=False):
     """attention_tiled() without the head permutes: q, k, v [B,S,E] as the
     projections wrote them (three tensors, or three column views of one packed
     [B,S,3E]), result [B,S,E] as the output projection reads it.  Head h is
     columns [h*hd, (h+1)*hd); key_bias is [B,S].  Same dropout counter and
-    keep decisions as attention_tiled on the permuted operands.
+    keep decisions as attention_tiled on the permuted operands; is_causal as
+    there.
 
     packed names the [B,S,3E] tensor q, k, v were split from, for a caller
     whose q._base is not that tensor (a view of a view reports the root)."""
@@ -764,7 +770,7 @@ def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
     if base is not None:
         q, k, v = base, None, None
     return AttnHeadsFn.apply(q, k, v, int(heads), float(scale), p, seed,
-                             offset_t, _key_bias_arg(key_bias))
+                             offset_t, _key_bias_arg(key_bias), bool(is_causal))
 
 
 class AttnProbsFn(Function):

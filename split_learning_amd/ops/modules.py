@@ -149,15 +149,23 @@ class HipMultiheadAttention(nn.MultiheadAttention):
     """
 
     def forward(self, query, key, value, **kwargs):  # type: ignore[override]
-        # The native path computes plain or key-padded self-attention and
-        # returns no weights.  What it cannot honour goes to the stock
-        # forward: an attn_mask, is_causal, or weights explicitly asked for
-        # (need_weights left at its default keeps the native path, as before).
+        # The native path computes plain, key-padded or causal self-attention
+        # and returns no weights.  Causal is torch's hint form: is_causal=True
+        # WITH an attn_mask, whose contents are trusted to be causal and not
+        # read (the tiled kernels mask by position, at every S).  What the
+        # path cannot honour goes to the stock forward: an attn_mask without
+        # is_causal, is_causal without an attn_mask (the stock forward
+        # raises), a causal call at a head size the tiled kernels do not
+        # take, or weights explicitly asked for (need_weights left at its
+        # default keeps the native path, as before).
+        causal = (bool(kwargs.get("is_causal", False))
+                  and kwargs.get("attn_mask") is not None)
         if (not _use_native("attn", query) or (query is not key)
                 or (key is not value) or not self.batch_first
                 or query.dim() != 3
-                or kwargs.get("attn_mask") is not None
-                or kwargs.get("is_causal", False)
+                or (causal and not _causal_heads_ok(query, self.num_heads))
+                or (not causal and (kwargs.get("attn_mask") is not None
+                                    or kwargs.get("is_causal", False)))
                 or kwargs.get("need_weights", False)):
             return super().forward(query, key, value, **kwargs)
         x = query  # [B, S, E]
@@ -168,7 +176,14 @@ class HipMultiheadAttention(nn.MultiheadAttention):
         qkv = hf.linear(x, self.in_proj_weight, self.in_proj_bias)  # [B,S,3E]
         q, k, v = qkv.split(E, dim=-1)
         scale = 1.0 / math.sqrt(hd)
-        if _heads_attn_route(q, k, v, H):
+        if causal:
+            # qkv is dense [B,S,3E] with hd in {32, 64}: hf.attn_heads_ok holds
+            ctxv = hf.attention_heads(q, k, v, H, scale,
+                                      dropout_p=self.dropout,
+                                      training=self.training,
+                                      key_bias=key_bias, packed=qkv,
+                                      is_causal=True)
+        elif _heads_attn_route(q, k, v, H):
             # tiled kernels on qkv's own layout: the three column views go in
             # as they are, the context comes out as out_proj reads it
             ctxv = hf.attention_heads(q, k, v, H, scale,
@@ -282,16 +297,30 @@ def _heads_attn_route(q, k, v, heads) -> bool:
             and (q.shape[1] >= _TILED_MIN_S or _FATTN_TILED))
 
 
+def _causal_heads_ok(x, heads) -> bool:
+    """hf.attn_heads_ok for the q, k, v that in_proj will write from x
+    [B,S,E]: thirds of one dense fp32 [B,S,3E], so only the shape rules are
+    left.  No S threshold: causal has no other native route."""
+    B, S, E = x.shape
+    return ("fattn" not in _DBG_TORCH and x.dtype == torch.float32 and S >= 1
+            and E % heads == 0 and E // heads in (32, 64)
+            and B * heads <= 65535)
+
+
 def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
                    scale: Optional[float] = None, key_bias=None,
-                   heads: int = 1):
+                   heads: int = 1, is_causal: bool = False):
     """scaled-dot-product attention on [B*H, S, hd] tensors via HIP kernels.
 
     key_bias ([B, S] additive float, B = q.shape[0] // heads) is added to the
     scaled scores of every head and query row of its sample before the
-    softmax: a padding mask.  Without it every route is the unmasked one."""
+    softmax: a padding mask.  Without it every route is the unmasked one.
+    is_causal: query row i attends to keys <= i, with or without key_bias."""
     hd = q.shape[-1]
     s = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if is_causal:
+        return _attention_core_causal(q, k, v, dropout_p, training, s,
+                                      key_bias, heads)
     if key_bias is not None:
         return _attention_core_biased(q, k, v, dropout_p, training, s,
                                       key_bias, heads)
@@ -311,6 +340,35 @@ def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
             probs = hf.dropout(probs, dropout_p, training)
         return hf.matmul_f32(probs, v)
     scores = torch.matmul(q, k.transpose(-1, -2)) * s
+    probs = F.softmax(scores, dim=-1)
+    if dropout_p > 0.0:
+        probs = F.dropout(probs, dropout_p, training)
+    return torch.matmul(probs, v)
+
+
+def _attention_core_causal(q, k, v, dropout_p, training, s, key_bias, heads):
+    """attention_core with a causal mask.  The tiled kernels are the only
+    native route that can mask causally (they walk the key tiles up to the
+    diagonal), so they take every S their operand rule admits; what they
+    cannot take is the plain torch chain with a triu(-inf) mask."""
+    BH, S = q.shape[0], q.shape[1]
+    if key_bias is not None and (
+            q.dim() != 3 or BH % heads != 0
+            or tuple(key_bias.shape) != (BH // heads, S)):
+        raise ValueError(
+            f"key_bias must be [B*H / heads, S] for q {tuple(q.shape)} and "
+            f"heads={heads}, got {tuple(key_bias.shape)}")
+    if (_use_native("attn", q) and "fattn" not in _DBG_TORCH
+            and hf.attn_tiled_ok(q, k, v)):
+        return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
+                                  training=training, key_bias=key_bias,
+                                  heads=heads, is_causal=True)
+    scores = torch.matmul(q, k.transpose(-1, -2)) * s
+    if key_bias is not None:
+        scores = (scores.view(BH // heads, heads, S, S)
+                  + key_bias.to(scores.dtype)[:, None, None, :]).view(BH, S, S)
+    scores = scores + torch.full((S, S), float("-inf"), dtype=scores.dtype,
+                                 device=scores.device).triu(diagonal=1)
     probs = F.softmax(scores, dim=-1)
     if dropout_p > 0.0:
         probs = F.dropout(probs, dropout_p, training)
