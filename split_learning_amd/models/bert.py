@@ -23,6 +23,7 @@ from ..ops.modules import (HipDropout, HipEmbedding, HipGELU, HipLayerNorm,
                            HipLinear, HipTanh, _heads_attn_route,
                            attention_core)
 from ..ops import functional as hf
+from .lora import qkv_adapters
 from .partitioned import PartitionedModel
 
 
@@ -79,17 +80,24 @@ class BertSdpaSelfAttention(nn.Module):
     def forward(self, hidden_states, attention_mask=None):
         B, S, E = hidden_states.shape
         H, hd = self.num_attention_heads, self.attention_head_size
-        q, k, v = (self.query(hidden_states), self.key(hidden_states),
-                   self.value(hidden_states))
+        # three LoRA projections: one grouped adapter launch writes q, k, v as
+        # the column thirds of one [B,S,3E] tensor (models/lora.py)
+        qkv = qkv_adapters(hidden_states, self.query, self.key, self.value)
+        if qkv is not None:
+            q, k, v = qkv.split(self.all_head_size, dim=-1)
+        else:
+            q, k, v = (self.query(hidden_states), self.key(hidden_states),
+                       self.value(hidden_states))
         if q.dim() == 3 and _heads_attn_route(q, k, v, H):
             # tiled kernels on the projections' [B,S,E] layout: no head
-            # permutes; same additive mask as below
+            # permutes; same additive mask as below.  From the packed tensor
+            # attention returns one packed gradient
             key_bias = None if attention_mask is None else \
                 (1.0 - attention_mask.to(torch.float32)) * -10000.0
             return hf.attention_heads(q, k, v, H, 1.0 / math.sqrt(hd),
                                       dropout_p=self.dropout.p,
                                       training=self.training,
-                                      key_bias=key_bias)
+                                      key_bias=key_bias, packed=qkv)
         q = q.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         k = k.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         v = v.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()

@@ -22,6 +22,11 @@ from ..ops.modules import _DBG_TORCH, HipDropout
 # profiles/SUMMARY.md "Fused LoRA adapter")
 _LORA_CHAIN = (os.environ.get("SLK_LORA", "") == "chain"
                or bool(_DBG_TORCH & {"linear", "dropout"}))
+# BERT's self-attention groups its query, key and value adapters into one
+# launch (qkv_adapters below, hf.lora_qkv).  SLK_LORA=qkv asks for that route;
+# SLK_LORA=single names the fused adapter per projection (A/B measurement;
+# profiles/SUMMARY.md "QKV LoRA adapter")
+_LORA_SINGLE = os.environ.get("SLK_LORA", "") != "qkv"
 
 
 class LoRALinear(nn.Module):
@@ -59,6 +64,27 @@ class LoRALinear(nn.Module):
 
     def merged_weight(self) -> torch.Tensor:
         return self.base.weight + (self.lora_B @ self.lora_A) * self.scaling
+
+
+def qkv_adapters(x, query, key, value):
+    """hf.lora_qkv's result for three projections of x, or None where the
+    grouped route does not apply: all three LoRALinear with one r, scaling
+    and dropout p on operands lora_qkv_ok takes, x on the GPU, and neither
+    the chain nor the single route asked for."""
+    mods = (query, key, value)
+    if (not x.is_cuda or _LORA_CHAIN or _LORA_SINGLE
+            or not all(isinstance(m, LoRALinear) for m in mods)
+            or any((m.r, m.scaling, m.lora_dropout.p, m.training)
+                   != (query.r, query.scaling, query.lora_dropout.p,
+                       query.training) for m in mods)):
+        return None
+    from ..ops import functional as hf
+    ws = [m.base.weight for m in mods]
+    las, lbs = [m.lora_A for m in mods], [m.lora_B for m in mods]
+    if not hf.lora_qkv_ok(x, ws, las, lbs):
+        return None
+    return hf.lora_qkv(x, ws, [m.base.bias for m in mods], las, lbs,
+                       query.scaling, query.lora_dropout.p, query.training)
 
 
 def apply_lora(model: nn.Module, r: int = 8, alpha: int = 16, dropout: float = 0.1,

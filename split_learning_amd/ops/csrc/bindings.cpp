@@ -121,6 +121,18 @@ std::vector<at::Tensor> lora_bwd(const at::Tensor&, const at::Tensor&,
                                  double, double, int64_t,
                                  c10::optional<at::Tensor>);
 int lora_wgrad_slabs(int64_t, int64_t, int64_t);
+std::vector<at::Tensor> lora_qkv_fwd(at::Tensor, const std::vector<at::Tensor>&,
+                                     const at::Tensor&,
+                                     const std::vector<at::Tensor>&,
+                                     const std::vector<at::Tensor>&, double,
+                                     double, int64_t, c10::optional<at::Tensor>);
+std::vector<at::Tensor> lora_qkv_bwd(const at::Tensor&, const at::Tensor&,
+                                     const std::vector<at::Tensor>&,
+                                     const std::vector<at::Tensor>&,
+                                     const at::Tensor&, c10::optional<at::Tensor>,
+                                     double, double, int64_t,
+                                     c10::optional<at::Tensor>);
+int lora_qkv_wgrad_slabs(int64_t, int64_t, int64_t);
 // loss.hip
 at::Tensor softmax_fwd(const at::Tensor&);
 at::Tensor softmax_bwd(const at::Tensor&, const at::Tensor&);
@@ -254,6 +266,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("offset") = py::none());
   m.def("lora_wgrad_slabs", &slk::lora_wgrad_slabs, py::arg("M"), py::arg("K"),
         py::arg("N"));
+  m.def("lora_qkv_fwd", &slk::lora_qkv_fwd, py::arg("out"), py::arg("base"),
+        py::arg("x"), py::arg("lora_As"), py::arg("lora_Bs"), py::arg("scaling"),
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = py::none());
+  m.def("lora_qkv_bwd", &slk::lora_qkv_bwd, py::arg("g"), py::arg("x"),
+        py::arg("lora_As"), py::arg("lora_Bs"), py::arg("xa"), py::arg("gx"),
+        py::arg("scaling"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = py::none());
+  m.def("lora_qkv_wgrad_slabs", &slk::lora_qkv_wgrad_slabs, py::arg("M"),
+        py::arg("K"), py::arg("N"));
   m.def("softmax_fwd", &slk::softmax_fwd);
   m.def("softmax_bwd", &slk::softmax_bwd);
   m.def("ce_fwd", &slk::ce_fwd);

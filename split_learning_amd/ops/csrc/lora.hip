@@ -68,6 +68,44 @@
 //   lora_wgrad_kernel<nodrop>         54    16      16384        0      7
 // A block is one wave per SIMD, so the row kernel's 256 blocks at M = 4096 sit
 // far below these limits: what it has in flight is its own batched loads.
+//
+// QKV-grouped kernels (lora_qkv_*): the query, key and value adapters of one
+// self-attention block share x, M, K, N, r, scaling and p and differ in their
+// small operands and their dropout offset (o, o+1, o+2: what three successive
+// single calls read).  Same lane maps, same interleaves, same summation orders
+// as above, so every output element of the forward has the bits three single
+// calls give it; what changes is what is read and written how often:
+//   row, forward   a lane's 16 bytes of x are loaded once per step, masked
+//                  three times and fed to three accumulators against A_q,
+//                  A_k, A_v; xa is [3][M][r].  The up phase reads the three
+//                  dense base products and writes Out_j = Base_j + scaling *
+//                  T_j B_j^T into the column thirds of ONE packed [M,3N]
+//                  tensor, the layout the head-strided attention kernels
+//                  read.  (Base and Out are separate pointers with their own
+//                  row strides: the base GEMMs of both routes keep their
+//                  dense stores, and the traffic is the in-place form's: one
+//                  read, one write per element.)  The thirds are walked one
+//                  after the other, the waves interleaving over each third's
+//                  tiles: T_j^T is then four registers, not twelve selected
+//                  at run time.
+//   row, backward  reads the thirds of the packed gradient in place (row
+//                  stride given), gxa is [3][M][r]; the up phase adds all
+//                  three masked updates to Base = sum_j g_j W_j in one read
+//                  and one write of gx.
+//   weight grad    a gA block streams its slab of x once into gA_q, gA_k,
+//                  gA_v (three masks on the one load, twelve accumulators);
+//                  the gB blocks walk the 3 * ceil(N/64) chunks of the packed
+//                  gradient.  Slabs are [slabs][3][r][K] and [slabs][3][N][r],
+//                  so slab_reduce_pair sums all six outputs in one launch.
+//   kernel                          VGPR  AGPR  LDS bytes  scratch  waves/SIMD
+//   lora_qkv_row_kernel<fwd, drop>   114    12      16320        0      4
+//   lora_qkv_row_kernel<fwd, nodrop>  98    12      16320        0      4
+//   lora_qkv_row_kernel<bwd, drop>   161    12      16320        0      2
+//   lora_qkv_row_kernel<bwd, nodrop> 148    12      16320        0      3
+//   lora_qkv_wgrad_kernel<drop>       98    60      16384        0      3
+//   lora_qkv_wgrad_kernel<nodrop>     72    48      16384        0      4
+// Scratch is 0 at the single kernels' batch depths (4 row steps, 8 row
+// groups), so they are kept; a block is still one wave per SIMD.
 #include <type_traits>
 
 #include "torch_util.h"
@@ -302,11 +340,341 @@ __global__ __launch_bounds__(256) void lora_wgrad_kernel(LoraWgradArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// QKV-grouped adapters: j = 0, 1, 2 is query, key, value
+// ---------------------------------------------------------------------------
+
+constexpr int LQ = 3;
+
+struct LoraQkvRowArgs {
+  const float* in;         // forward x [M,C]; backward the packed gradient,
+  long ld_in;              //   third j at in + j*C; ld_in: its row stride
+  const float* wd[LQ];     // forward A_j [r,C]; backward B_j [C,r]
+  const float* wu[LQ];     // forward B_j [D,r]; backward A_j [r,D]
+  float* t;                // [3][M][r]: xa or gxa, written
+  const float* base[LQ];   // forward: x W_j^T + b_j [M,D]; backward: base[0]
+  long ld_base;            //   = sum_j g_j W_j [M,D]; ld_base: row stride
+  float* out;              // forward: packed [M,3D], third j at out + j*D;
+  long ld_out;             //   backward: gx [M,D]; null skips the up phase
+  const long* offset_in;   // forward: the live counter, already advanced by 3;
+  long* offset_out;        //   backward: what the forward wrote here, the
+  uint64_t seed;           //   offset of q's mask (k: + 1, v: + 2)
+  int M, C, D, r;
+  float tscale, ucoef, p, inv_keep;
+};
+
+template <bool BWD> struct LqDown { f32x4 v[BWD ? LQ : 1], w[LQ]; };
+struct LqUp { f32x4 base; float wa[LQ][4]; };
+
+template <bool BWD, bool DROPOUT>
+__global__ __launch_bounds__(256) void lora_qkv_row_kernel(LoraQkvRowArgs a) {
+  __shared__ float part[LQ][4][LR_ROWS][LR_RMAX + 1];
+  __shared__ float Ts[LQ][LR_ROWS][LR_RMAX + 1];
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int M = a.M, C = a.C, D = a.D, r = a.r;
+  const int row0 = blockIdx.x * LR_ROWS;
+  const int row = row0 + c;
+  const bool row_ok = row < M;
+  const long rowc = row_ok ? row : M - 1;
+
+  uint64_t offset = 0;
+  if (DROPOUT) {
+    offset = (uint64_t)a.offset_in[0];
+    if (!BWD) {
+      offset -= LQ - 1;
+      if (blockIdx.x == 0 && tid == 0) a.offset_out[0] = (long)offset;
+    }
+  }
+
+  // ---- down: T_j = In_j Wd_j (forward: one In), the waves interleaved over C
+  f32x4 acc[LQ] = {};
+  {
+    const float* inrow = a.in + rowc * a.ld_in;
+    const int jc = min(c, r - 1);
+    const bool j_ok = c < r;
+    slk_batched<4, LqDown<BWD>>(
+        0, (C + 63) / 64, 1,
+        [&](int s) {
+          const int col = 64 * s + 16 * wid + 4 * g;
+          const bool ok = col < C;
+          const int cc = ok ? col : 0;
+          LqDown<BWD> l;
+          #pragma unroll
+          for (int j = 0; j < (BWD ? LQ : 1); ++j) {
+            l.v[j] = *reinterpret_cast<const f32x4*>(inrow + (long)j * C + cc);
+            if (!(ok && row_ok)) l.v[j] = f32x4{};
+          }
+          #pragma unroll
+          for (int j = 0; j < LQ; ++j) {
+            if (!BWD) {
+              l.w[j] = *reinterpret_cast<const f32x4*>(a.wd[j] + (long)jc * C + cc);
+            } else {
+              #pragma unroll
+              for (int e = 0; e < 4; ++e)
+                l.w[j][e] = a.wd[j][(long)(cc + e) * r + jc];
+            }
+            if (!(ok && j_ok)) l.w[j] = f32x4{};
+          }
+          return l;
+        },
+        [&](int s, const LqDown<BWD>& l) {
+          const int col = 64 * s + 16 * wid + 4 * g;
+          #pragma unroll
+          for (int j = 0; j < LQ; ++j) {
+            const f32x4 v = lr_drop<DROPOUT && !BWD>(
+                l.v[BWD ? j : 0], a.seed, offset + j, (uint64_t)rowc * C + col,
+                a.p, a.inv_keep);
+            #pragma unroll
+            for (int e = 0; e < 4; ++e) acc[j] = lr_mfma(v[e], l.w[j][e], acc[j]);
+          }
+        });
+  }
+  #pragma unroll
+  for (int j = 0; j < LQ; ++j) {
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) part[j][wid][4 * g + q][c] = acc[j][q];
+  }
+  __syncthreads();
+  {
+    const int i = tid >> 4, k = tid & 15;
+    #pragma unroll
+    for (int j = 0; j < LQ; ++j) {
+      const float t = (((part[j][0][i][k] + part[j][1][i][k]) + part[j][2][i][k]) +
+                       part[j][3][i][k]) * a.tscale;
+      Ts[j][i][k] = t;
+      if (row0 + i < M && k < r) a.t[((long)j * M + row0 + i) * r + k] = t;
+    }
+  }
+  if (a.out == nullptr) return;
+  __syncthreads();
+
+  const int tiles = (D + 15) / 16;
+  if constexpr (!BWD) {
+    // ---- up: Out_j^T = Base_j^T + coef * Wu_j^T T_j^T, third after third ----
+    #pragma unroll
+    for (int j = 0; j < LQ; ++j) {
+      float tb[4];
+      #pragma unroll
+      for (int ks = 0; ks < 4; ++ks) tb[ks] = Ts[j][c][4 * ks + g];
+      const float* baserow = a.base[j] + rowc * a.ld_base;
+      float* outrow = a.out + rowc * a.ld_out + (long)j * D;
+      const float* wu = a.wu[j];
+      slk_batched<4, LrUp>(
+          wid, tiles, 4,
+          [&](int tile) {
+            const int dcol = 16 * tile + c;
+            const bool d_ok = dcol < D;
+            const int dc = d_ok ? dcol : 0;
+            LrUp l;
+            #pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+              const int k = 4 * ks + g;
+              const float w = wu[(long)dc * r + min(k, r - 1)];
+              l.wa[ks] = d_ok && k < r ? w : 0.f;
+            }
+            l.base = *reinterpret_cast<const f32x4*>(
+                baserow + min(16 * tile + 4 * g, D - 4));
+            return l;
+          },
+          [&](int tile, const LrUp& l) {
+            f32x4 u = {};
+            #pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+              if (4 * ks < r) u = lr_mfma(l.wa[ks], tb[ks], u);
+            const int col = 16 * tile + 4 * g;
+            u = u * a.ucoef;
+            if (row_ok && col < D)
+              *reinterpret_cast<f32x4*>(outrow + col) = l.base + u;
+          });
+    }
+  } else {
+    // ---- up: gx^T = Base^T + sum_j keep_j/(1-p) o (A_j^T gxa_j^T) ----
+    float tb[LQ][4];
+    #pragma unroll
+    for (int j = 0; j < LQ; ++j) {
+      #pragma unroll
+      for (int ks = 0; ks < 4; ++ks) tb[j][ks] = Ts[j][c][4 * ks + g];
+    }
+    const float* baserow = a.base[0] + rowc * a.ld_base;
+    float* outrow = a.out + rowc * a.ld_out;
+    slk_batched<4, LqUp>(
+        wid, tiles, 4,
+        [&](int tile) {
+          const int dcol = 16 * tile + c;
+          const bool d_ok = dcol < D;
+          const int dc = d_ok ? dcol : 0;
+          LqUp l;
+          #pragma unroll
+          for (int j = 0; j < LQ; ++j) {
+            #pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+              const int k = 4 * ks + g;
+              const float w = a.wu[j][(long)min(k, r - 1) * D + dc];
+              l.wa[j][ks] = d_ok && k < r ? w : 0.f;
+            }
+          }
+          l.base = *reinterpret_cast<const f32x4*>(
+              baserow + min(16 * tile + 4 * g, D - 4));
+          return l;
+        },
+        [&](int tile, const LqUp& l) {
+          const int col = 16 * tile + 4 * g;
+          f32x4 s = l.base;
+          #pragma unroll
+          for (int j = 0; j < LQ; ++j) {
+            f32x4 u = {};
+            #pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+              if (4 * ks < r) u = lr_mfma(l.wa[j][ks], tb[j][ks], u);
+            u = u * a.ucoef;
+            s += lr_drop<DROPOUT>(u, a.seed, offset + j, (uint64_t)rowc * D + col,
+                                  a.p, a.inv_keep);
+          }
+          if (row_ok && col < D) *reinterpret_cast<f32x4*>(outrow + col) = s;
+        });
+  }
+}
+
+struct LoraQkvWgradArgs {
+  const float* x;          // [M,K]
+  const float* g;          // packed gradient, third j at g + j*N
+  long ld_g;               // its row stride
+  const float* xa;         // [3][M][r]
+  const float* gxa;        // [3][M][r]
+  float* slab_a;           // [slabs][3][r][K]
+  float* slab_b;           // [slabs][3][N][r]
+  const long* offset;      // the offset the forward saved (q's)
+  uint64_t seed;
+  int M, K, N, r, rows_per_slab;
+  float scaling, p, inv_keep;
+};
+
+template <int NJ> struct LqwStep { f32x4 big; float small[NJ]; };
+
+// acc[j][e] += Small_j^T Big over rows m_lo .. m_hi of one 64-column chunk:
+// lora_wgrad_kernel's loop with NJ small operands (small + j * small_step)
+// against the one load of Big; MASKED redraws mask j at offset + j
+template <int NJ, bool MASKED>
+__device__ __forceinline__ void lqw_accumulate(
+    const float* __restrict__ big, long ld, int C, int cc, bool col_ok,
+    const float* __restrict__ small, long small_step, int r, int m_lo, int m_hi,
+    uint64_t seed, uint64_t offset, float p, float inv_keep,
+    f32x4 (&acc)[NJ][4]) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int jc = min(c, r - 1);
+  const bool j_ok = c < r;
+  slk_batched<8, LqwStep<NJ>>(
+      m_lo + 4 * wid, m_hi, 16,
+      [&](int m4) {
+        const int m = m4 + g;
+        const bool m_ok = m < m_hi;
+        const long mc = m_ok ? m : m_hi - 1;
+        LqwStep<NJ> l;
+        l.big = *reinterpret_cast<const f32x4*>(big + mc * ld + cc);
+        if (!(m_ok && col_ok)) l.big = f32x4{};
+        #pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          l.small[j] = small[j * small_step + mc * r + jc];
+          if (!(m_ok && j_ok)) l.small[j] = 0.f;
+        }
+        return l;
+      },
+      [&](int m4, const LqwStep<NJ>& l) {
+        const long mc = min(m4 + g, m_hi - 1);
+        #pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const f32x4 v = lr_drop<MASKED>(l.big, seed, offset + j,
+                                          (uint64_t)mc * C + cc, p, inv_keep);
+          #pragma unroll
+          for (int e = 0; e < 4; ++e)
+            acc[j][e] = lr_mfma(l.small[j], v[e], acc[j][e]);
+        }
+      });
+}
+
+// the four waves' partials of one output tile, summed in wave order: thread
+// (q = wid, lane) receives Out[4g + q][col .. col + 3].  Block-wide; red is
+// free again on return
+__device__ __forceinline__ f32x4 lqw_wave_sum(float (&red)[4][4][4][64],
+                                              const f32x4 (&acc)[4]) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  #pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) red[wid][e][q][lane] = acc[e][q];
+  }
+  __syncthreads();
+  f32x4 s;
+  #pragma unroll
+  for (int e = 0; e < 4; ++e)
+    s[e] = ((red[0][e][wid][lane] + red[1][e][wid][lane]) +
+            red[2][e][wid][lane]) + red[3][e][wid][lane];
+  __syncthreads();
+  return s;
+}
+
+template <bool DROPOUT>
+__global__ __launch_bounds__(256) void lora_qkv_wgrad_kernel(LoraQkvWgradArgs a) {
+  __shared__ float red[4][4][4][64];   // [wave][e][q][lane]
+
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int r = a.r;
+  const int chunks_k = (a.K + LW_COLS - 1) / LW_COLS;
+  const int chunks_n = (a.N + LW_COLS - 1) / LW_COLS;
+  const bool job_a = (int)blockIdx.x < chunks_k;          // block-uniform
+  const int m_lo = blockIdx.y * a.rows_per_slab;
+  const int m_hi = min(a.M, m_lo + a.rows_per_slab);
+  const long mr = (long)a.M * r;
+  const int jr = 4 * g + wid;           // the output row lqw_wave_sum hands over
+
+  if (job_a) {
+    const int col = LW_COLS * blockIdx.x + 4 * c;
+    const bool col_ok = col < a.K;
+    uint64_t offset = 0;
+    if (DROPOUT) offset = (uint64_t)a.offset[0];
+    f32x4 acc[LQ][4] = {};
+    lqw_accumulate<LQ, DROPOUT>(a.x, a.K, a.K, col_ok ? col : 0, col_ok, a.gxa,
+                                mr, r, m_lo, m_hi, a.seed, offset, a.p,
+                                a.inv_keep, acc);
+    #pragma unroll
+    for (int j = 0; j < LQ; ++j) {
+      const f32x4 s = lqw_wave_sum(red, acc[j]);
+      if (jr < r && col_ok)
+        *reinterpret_cast<f32x4*>(
+            a.slab_a + (((long)blockIdx.y * LQ + j) * r + jr) * a.K + col) = s;
+    }
+  } else {
+    const int chunk = blockIdx.x - chunks_k;
+    const int j = chunk / chunks_n;
+    const int col = LW_COLS * (chunk - j * chunks_n) + 4 * c;
+    const bool col_ok = col < a.N;
+    f32x4 acc[1][4] = {};
+    lqw_accumulate<1, false>(a.g + (long)j * a.N, a.ld_g, a.N, col_ok ? col : 0,
+                             col_ok, a.xa + j * mr, 0, r, m_lo, m_hi, 0, 0, 0.f,
+                             1.f, acc);
+    const f32x4 s = lqw_wave_sum(red, acc[0]);
+    if (jr < r && col_ok) {
+      float* o = a.slab_b + (((long)blockIdx.y * LQ + j) * a.N + col) * r + jr;
+      #pragma unroll
+      for (int e = 0; e < 4; ++e) o[(long)e * r] = s[e] * a.scaling;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 
 // slabs of M for the weight-gradient grid: enough blocks to fill the chip, at
-// least 64 rows (four k-steps a wave) per slab, a multiple of 16 rows each
+// least 64 rows (four k-steps a wave) per slab, a multiple of 16 rows each.
+// The QKV grid takes the same count although it has 3 * ceil(N/64) gB
+// chunks: its time is its gA blocks', which draw three masks an element, and
+// with the slabs cut to 512 / all chunks (10 at K = N = 768) only 120 of them
+// shared that work: 58.1 us measured against 3 * 14.0 us for three single
+// launches at M = 4096.  Sized by one adapter's chunks there are 252.
 static int lw_rows_per_slab(long M, long K, long N) {
   const long chunks = ceil_div(K, LW_COLS) + ceil_div(N, LW_COLS);
   long slabs = std::max<long>(1, LW_TARGET / chunks);
@@ -485,6 +853,181 @@ std::vector<at::Tensor> lora_bwd(const at::Tensor& g, const at::Tensor& x,
     hipLaunchKernelGGL(lora_wgrad_kernel<true>, grid, dim3(256), 0, stream, w);
   else
     hipLaunchKernelGGL(lora_wgrad_kernel<false>, grid, dim3(256), 0, stream, w);
+  slab_reduce_pair(w.slab_a, slabs, gA.data_ptr<float>(), gA.numel(), w.slab_b,
+                   slabs, gB.data_ptr<float>(), gB.numel(), stream);
+  return {gA, gB};
+}
+
+// ---- QKV-grouped adapters ----
+
+int lora_qkv_wgrad_slabs(int64_t M, int64_t K, int64_t N) {
+  TORCH_CHECK(M >= 1 && K >= 1 && N >= 1, "lora_qkv_wgrad_slabs: M, K, N >= 1");
+  return ceil_div(M, lw_rows_per_slab(M, K, N));
+}
+
+// x and the three identically shaped adapters, in q, k, v order
+static LoraProblem lora_qkv_check(const at::Tensor& x,
+                                  const std::vector<at::Tensor>& As,
+                                  const std::vector<at::Tensor>& Bs, double p,
+                                  const c10::optional<at::Tensor>& offset,
+                                  const char* who) {
+  TORCH_CHECK(As.size() == LQ && Bs.size() == LQ, who,
+              ": three lora_A and three lora_B (query, key, value)");
+  const LoraProblem pr = lora_check(x, As[0], Bs[0], p, offset, who);
+  for (int j = 1; j < LQ; ++j) {
+    lr_operand(As[j], x, {pr.r, pr.K}, who, "lora_A");
+    lr_operand(Bs[j], x, {pr.N, pr.r}, who, "lora_B");
+  }
+  return pr;
+}
+
+template <bool BWD>
+static void lora_qkv_row_launch(const LoraQkvRowArgs& a, bool drop,
+                                hipStream_t stream) {
+  const dim3 grid(ceil_div(a.M, LR_ROWS));
+  if (drop)
+    hipLaunchKernelGGL((lora_qkv_row_kernel<BWD, true>), grid, dim3(256), 0,
+                       stream, a);
+  else
+    hipLaunchKernelGGL((lora_qkv_row_kernel<BWD, false>), grid, dim3(256), 0,
+                       stream, a);
+}
+
+// out [M,3N]: third j = base[j] + scaling * (dropout_j(x) A_j^T) B_j^T, where
+// base[j] [M,N] = x W_j^T + b_j and dropout_j draws at the counter value the
+// j-th of three successive lora_fwd calls would have read: offset is the live
+// counter, already advanced by 3.
+// -> {xa [3,M,r], offset_used [1] int64: q's offset (empty when p == 0)}
+std::vector<at::Tensor> lora_qkv_fwd(at::Tensor out,
+                                     const std::vector<at::Tensor>& base,
+                                     const at::Tensor& x,
+                                     const std::vector<at::Tensor>& As,
+                                     const std::vector<at::Tensor>& Bs,
+                                     double scaling, double p, int64_t seed,
+                                     c10::optional<at::Tensor> offset) {
+  const char* who = "lora_qkv_fwd";
+  const LoraProblem pr = lora_qkv_check(x, As, Bs, p, offset, who);
+  TORCH_CHECK(base.size() == LQ, who, ": three base products");
+  for (int j = 0; j < LQ; ++j) lr_operand(base[j], x, {pr.M, pr.N}, who, "base");
+  lr_operand(out, x, {pr.M, LQ * pr.N}, who, "out");
+  auto xa = at::empty({LQ, pr.M, pr.r}, x.options());
+  auto used = at::empty({pr.drop ? 1 : 0}, x.options().dtype(at::kLong));
+  if (pr.M == 0) return {xa, used};
+  LoraQkvRowArgs a = {};
+  a.in = x.data_ptr<float>();
+  a.ld_in = pr.K;
+  for (int j = 0; j < LQ; ++j) {
+    a.wd[j] = As[j].data_ptr<float>();
+    a.wu[j] = Bs[j].data_ptr<float>();
+    a.base[j] = base[j].data_ptr<float>();
+  }
+  a.t = xa.data_ptr<float>();
+  a.ld_base = pr.N;
+  a.out = out.data_ptr<float>();
+  a.ld_out = LQ * pr.N;
+  a.offset_in = pr.drop ? offset->data_ptr<long>() : nullptr;
+  a.offset_out = pr.drop ? used.data_ptr<long>() : nullptr;
+  a.seed = pr.drop ? (uint64_t)seed : 0;
+  a.M = (int)pr.M;
+  a.C = (int)pr.K;
+  a.D = (int)pr.N;
+  a.r = (int)pr.r;
+  a.tscale = 1.f;
+  a.ucoef = (float)scaling;
+  a.p = pr.drop ? (float)p : 0.f;
+  a.inv_keep = pr.drop ? 1.0f / (1.0f - (float)p) : 1.f;   // = dropout_fwd_dev
+  lora_qkv_row_launch<false>(a, pr.drop,
+                             c10::hip::getCurrentHIPStream().stream());
+  return {xa, used};
+}
+
+// g [M,3N]: the packed gradient, unit column stride, any row stride that is a
+// multiple of 4 floats (attention's own buffer, or a view of a wider one).
+// gx [M,K] (= sum_j g_j W_j), when given, += sum_j keep_j/(1-p) o (gxa_j A_j)
+// in place, gxa_j = scaling * g_j B_j; -> {gA [3,r,K], gB [3,N,r]}.
+// offset: what lora_qkv_fwd returned
+std::vector<at::Tensor> lora_qkv_bwd(const at::Tensor& g, const at::Tensor& x,
+                                     const std::vector<at::Tensor>& As,
+                                     const std::vector<at::Tensor>& Bs,
+                                     const at::Tensor& xa,
+                                     c10::optional<at::Tensor> gx,
+                                     double scaling, double p, int64_t seed,
+                                     c10::optional<at::Tensor> offset) {
+  const char* who = "lora_qkv_bwd";
+  if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
+  const LoraProblem pr = lora_qkv_check(x, As, Bs, p, offset, who);
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat &&
+                  g.device() == x.device() && g.dim() == 2 &&
+                  g.size(0) == pr.M && g.size(1) == LQ * pr.N,
+              who, ": g must be a float32 cuda tensor [M,3N] on x's device");
+  const long ld_g = pr.M > 1 ? g.stride(0) : LQ * pr.N;
+  TORCH_CHECK(g.stride(1) == 1 && ld_g >= LQ * pr.N && ld_g % 4 == 0 &&
+                  (reinterpret_cast<uintptr_t>(g.data_ptr()) & 15) == 0,
+              who, ": g needs a unit column stride, a row stride >= 3N that is"
+                   " a multiple of 4, and a 16-byte aligned base");
+  lr_operand(xa, x, {LQ, pr.M, pr.r}, who, "xa");
+  if (gx.has_value()) lr_operand(*gx, x, {pr.M, pr.K}, who, "gx");
+  auto gA = at::empty({LQ, pr.r, pr.K}, x.options());
+  auto gB = at::empty({LQ, pr.N, pr.r}, x.options());
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  if (pr.M == 0) {
+    slk_zero_async(gA.data_ptr<float>(), gA.numel(), stream);
+    slk_zero_async(gB.data_ptr<float>(), gB.numel(), stream);
+    return {gA, gB};
+  }
+  auto gxa = at::empty({LQ, pr.M, pr.r}, x.options());
+  const float inv_keep = pr.drop ? 1.0f / (1.0f - (float)p) : 1.f;
+
+  LoraQkvRowArgs a = {};
+  a.in = g.data_ptr<float>();
+  a.ld_in = ld_g;
+  for (int j = 0; j < LQ; ++j) {
+    a.wd[j] = Bs[j].data_ptr<float>();
+    a.wu[j] = As[j].data_ptr<float>();
+  }
+  a.t = gxa.data_ptr<float>();
+  a.out = gx.has_value() ? gx->data_ptr<float>() : nullptr;
+  a.base[0] = a.out;
+  a.ld_base = a.ld_out = pr.K;
+  a.offset_in = pr.drop ? offset->data_ptr<long>() : nullptr;
+  a.seed = pr.drop ? (uint64_t)seed : 0;
+  a.M = (int)pr.M;
+  a.C = (int)pr.N;
+  a.D = (int)pr.K;
+  a.r = (int)pr.r;
+  a.tscale = (float)scaling;
+  a.ucoef = 1.f;
+  a.p = pr.drop ? (float)p : 0.f;
+  a.inv_keep = inv_keep;
+  lora_qkv_row_launch<true>(a, pr.drop, stream);
+
+  const int rows = lw_rows_per_slab(pr.M, pr.K, pr.N);
+  const int slabs = ceil_div(pr.M, rows);
+  auto slab = at::empty({(long)slabs * LQ * pr.r * (pr.K + pr.N)}, x.options());
+  LoraQkvWgradArgs w = {};
+  w.x = x.data_ptr<float>();
+  w.g = a.in;
+  w.ld_g = ld_g;
+  w.xa = xa.data_ptr<float>();
+  w.gxa = gxa.data_ptr<float>();
+  w.slab_a = slab.data_ptr<float>();
+  w.slab_b = w.slab_a + (long)slabs * LQ * pr.r * pr.K;   // r*K % 4 == 0: aligned
+  w.offset = a.offset_in;
+  w.seed = a.seed;
+  w.M = (int)pr.M;
+  w.K = (int)pr.K;
+  w.N = (int)pr.N;
+  w.r = (int)pr.r;
+  w.rows_per_slab = rows;
+  w.scaling = (float)scaling;
+  w.p = a.p;
+  w.inv_keep = inv_keep;
+  const dim3 grid(ceil_div(pr.K, LW_COLS) + LQ * ceil_div(pr.N, LW_COLS), slabs);
+  // same stream: gxa is complete before the weight-gradient kernel starts
+  if (pr.drop)
+    hipLaunchKernelGGL(lora_qkv_wgrad_kernel<true>, grid, dim3(256), 0, stream, w);
+  else
+    hipLaunchKernelGGL(lora_qkv_wgrad_kernel<false>, grid, dim3(256), 0, stream, w);
   slab_reduce_pair(w.slab_a, slabs, gA.data_ptr<float>(), gA.numel(), w.slab_b,
                    slabs, gB.data_ptr<float>(), gB.numel(), stream);
   return {gA, gB};

@@ -478,6 +478,104 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scaling, dropout_p=0.0,
                               p, seed, offset_t)
 
 
+class LoraQkvFn(Function):
+    """Three LoraLinearFn on one x (the query, key and value projections of a
+    self-attention block) with the adapters grouped: one launch forward
+    (lora_qkv_fwd), three backward (lora_qkv_bwd).  Returns the packed
+    [..., 3N] tensor whose column thirds are q, k, v, which is the layout
+    attention_heads(packed=) reads and whose gradient it returns whole.
+
+    The three base products keep linear()'s route and its dense stores
+    (neither route's GEMM targets a column third without a copy: the MFMA
+    store is dense row-major, and the BLAS route through a strided out= was
+    not measured); the forward kernel reads them and writes the thirds, so an
+    element is still read once and written once.  g_j W_j accumulate into one
+    gx buffer, each route in its own accumulate form, and read the thirds of
+    the packed gradient in place.  Saves x, the W_j, A_j, B_j, xa [3,M,r] and
+    the one-element offset of q's mask: no xd, mask or delta."""
+
+    @staticmethod
+    def forward(ctx, x, wq, wk, wv, bq, bk, bv, aq, ak, av, b_q, b_k, b_v,
+                scaling, p, seed, offset_t):
+        xs = x.reshape(-1, x.shape[-1]).contiguous()
+        ws, bs = (wq, wk, wv), (bq, bk, bv)
+        n, k = wq.shape
+        lib = 2.0 * xs.shape[0] * n * k >= _LIB_LIN_THRESH
+        base = [_F.linear(xs, w, b) if lib else native().linear_fwd(xs, w, b)
+                for w, b in zip(ws, bs)]
+        las = [t.contiguous() for t in (aq, ak, av)]
+        lbs = [t.contiguous() for t in (b_q, b_k, b_v)]
+        out = xs.new_empty(xs.shape[0], 3 * n)
+        xa, used = native().lora_qkv_fwd(out, base, xs, las, lbs, scaling, p,
+                                         seed, offset_t)
+        ctx.save_for_backward(xs, *ws, *las, *lbs, xa, used)
+        ctx.args = (scaling, p, seed, lib, [b is not None for b in bs], x.shape)
+        return out.reshape(*x.shape[:-1], 3 * n)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, *rest = ctx.saved_tensors
+        ws, las, lbs, (xa, used) = rest[0:3], rest[3:6], rest[6:9], rest[9:]
+        scaling, p, seed, lib, has_bias, x_shape = ctx.args
+        n = ws[0].shape[0]
+        g = gy.reshape(-1, 3 * n)
+        if g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
+            g = g.contiguous()
+        gs = g.split(n, dim=1)          # strided thirds: both GEMM routes and
+        gx = None                       # the kernels read them in place
+        if ctx.needs_input_grad[0]:
+            if lib:
+                gx = torch.matmul(gs[0], ws[0])
+                for j in (1, 2):
+                    gx.addmm_(gs[j], ws[j])
+            else:
+                gx = _matmul_raw(gs[0], ws[0])
+                for j in (1, 2):
+                    _matmul_raw(gs[j], ws[j], out=gx, accumulate=True)
+        gA, gB = native().lora_qkv_bwd(g, xs, las, lbs, xa, gx, scaling, p,
+                                       seed, used)
+        gw, gb = [None] * 3, [None] * 3
+        for j in range(3):
+            if ctx.needs_input_grad[1 + j]:
+                gw[j] = (torch.matmul(gs[j].t(), xs) if lib
+                         else _matmul_raw(gs[j], xs, trans_a=True))
+            if has_bias[j] and ctx.needs_input_grad[4 + j]:
+                # colsum_f32 reads a dense matrix: it copies its third
+                gb[j] = gs[j].sum(0) if lib else native().colsum_f32(gs[j])
+        if gx is not None:
+            gx = gx.reshape(x_shape)
+        return (gx, *gw, *gb, *gA.unbind(0), *gB.unbind(0), None, None, None,
+                None)
+
+
+def lora_qkv_ok(x, weights, lora_As, lora_Bs) -> bool:
+    """grouped adapter precondition: three (W, A, B) that each pass lora_ok
+    on x and have one shape (so one N, K and r)."""
+    if not len(weights) == len(lora_As) == len(lora_Bs) == 3:
+        return False
+    return all(lora_ok(x, w, a, b) and w.shape == weights[0].shape
+               and a.shape == lora_As[0].shape
+               for w, a, b in zip(weights, lora_As, lora_Bs))
+
+
+def lora_qkv(x, weights, biases, lora_As, lora_Bs, scaling, dropout_p=0.0,
+             training=False):
+    """[lora_linear(x, W_j, b_j, A_j, B_j) for j in q, k, v], concatenated
+    along the last dimension, on the grouped kernels.  The dropout counter
+    advances by 3 and the three masks are drawn at the values three
+    lora_linear calls in q, k, v order would have read, so the forward has
+    their bits and every later draw of the stream is where it was."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0:
+        counter = _counter_for(x.device)
+        counter.add_(3)
+        seed, offset_t = _DROPOUT_STATE["seed"], counter
+    else:
+        seed, offset_t = 0, None
+    return LoraQkvFn.apply(x, *weights, *biases, *lora_As, *lora_Bs,
+                           float(scaling), p, seed, offset_t)
+
+
 # ---------------------------------------------------------------------------
 # LayerNorm
 # ---------------------------------------------------------------------------
