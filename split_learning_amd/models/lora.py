@@ -48,7 +48,8 @@ class LoRALinear(nn.Module):
             if hf.lora_ok(x, self.base.weight, self.lora_A, self.lora_B):
                 return hf.lora_linear(x, self.base.weight, self.base.bias,
                                       self.lora_A, self.lora_B, self.scaling,
-                                      self.lora_dropout.p, self.training)
+                                      self.lora_dropout.p, self.training,
+                                      getattr(self.base, "compute", None))
         # the chain: CPU, shapes lora_ok turns away, and SLK_LORA=chain
         y = self.base(x)
         xd = self.lora_dropout(x)

@@ -21,6 +21,7 @@ BUILD_DIR = os.path.join(HERE, "_build")
 
 SOURCES = [
     "gemm_f32.hip",
+    "gemm_bf16.hip",
     "conv2d.hip",
     "wino.hip",
     "norm.hip",

@@ -8,6 +8,11 @@ at::Tensor matmul_f32(const at::Tensor&, const at::Tensor&, bool, bool,
 at::Tensor linear_fwd(const at::Tensor&, const at::Tensor&, c10::optional<at::Tensor>);
 at::Tensor colsum_f32(const at::Tensor&);
 int matmul_f32_slab_count(int, int, int, int);
+// gemm_bf16.hip
+at::Tensor linear_bf16_fwd(const at::Tensor&, const at::Tensor&,
+                           c10::optional<at::Tensor>, int64_t);
+at::Tensor linear_bf16_bwd_input(const at::Tensor&, const at::Tensor&, int64_t);
+at::Tensor linear_bf16_bwd_weight(const at::Tensor&, const at::Tensor&, int64_t);
 // wino.hip
 at::Tensor conv2d_wino(const at::Tensor&, const at::Tensor&,
                        c10::optional<at::Tensor>, int, bool);
@@ -163,6 +168,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum_f32", &slk::colsum_f32);
   m.def("matmul_f32_slab_count", &slk::matmul_f32_slab_count, py::arg("nb"),
         py::arg("M"), py::arg("N"), py::arg("K"));
+  m.def("linear_bf16_fwd", &slk::linear_bf16_fwd, py::arg("x"), py::arg("w"),
+        py::arg("bias") = py::none(), py::arg("tile") = -1);
+  m.def("linear_bf16_bwd_input", &slk::linear_bf16_bwd_input, py::arg("gy"),
+        py::arg("w"), py::arg("tile") = -1);
+  m.def("linear_bf16_bwd_weight", &slk::linear_bf16_bwd_weight, py::arg("gy"),
+        py::arg("x"), py::arg("tile") = -1);
   m.def("fast_div_eval", &slk::fast_div_eval, py::arg("d"), py::arg("max_n"),
         py::arg("ns"));
   m.def("conv2d_wino", &slk::conv2d_wino, py::arg("x"), py::arg("w"),

@@ -1,10 +1,18 @@
 """Autograd wrappers around the hand-written CDNA4 HIP kernels.
 
 Every Function here is GPU-only (callers dispatch CPU tensors to plain torch in
-split_learning_amd/ops/modules.py).  Numerics are exact fp32: the GEMM-shaped ops
-run on the f32-input MFMA path (v_mfma_f32_16x16x4_f32 — bitwise an fmaf chain),
-matching the reference's fp32 PyTorch math (reference trains pure fp32:
-src/train/VGG16.py has no dtype casts).
+split_learning_amd/ops/modules.py).  By default numerics are exact fp32: the
+GEMM-shaped ops run on the f32-input MFMA path (v_mfma_f32_16x16x4_f32 — bitwise
+an fmaf chain), matching the reference's fp32 PyTorch math (reference trains
+pure fp32: src/train/VGG16.py has no dtype casts).
+
+The one opt-in exception is the bf16-operand GEMM of linear() and lora_linear()
+(compute="bf16", or SLK_GEMM=bf16 for the calls that otherwise leave HIP for
+the platform BLAS): tensors, master weights, accumulation, bias, outputs and
+gradients stay fp32, and only the multiplier's operands are rounded to bf16
+(nearest even) on their way into LDS (csrc/gemm_bf16.hip).  Each product is
+then the fp32 sum of exact products of the rounded operands; what that does to
+a model's accuracy beyond the recorded BERT loss is not measured.
 
 Kernel-side entry points live in split_learning_amd/ops/csrc/ and are exported by
 the in-tree _sl_kernels extension (see ops/__init__.py loading policy).
@@ -123,7 +131,98 @@ class LinearFn(Function):
         return gx, gw, gb
 
 
-def linear(x, weight, bias=None):
+class Bf16LinearFn(Function):
+    """LinearFn on the bf16-operand MFMA GEMM (gemm_bf16.hip): NT forward, NN
+    for gx, TN (split into slabs, summed in order) for gW.  gb is colsum_f32
+    below _LIB_LIN_THRESH, as in LinearFn, and gys.sum(0) from there on, as on
+    LoraLinearFn's BLAS-sized route: colsum_f32 is one thread per column
+    walking all M rows, and at M = 3168 it alone took the KWT step from 5.6 to
+    32 ms (profiles/SUMMARY.md "bf16 MFMA GEMM").  Everything it reads, saves
+    and returns is fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        xs = x.reshape(-1, x.shape[-1]).contiguous()
+        y = native().linear_bf16_fwd(xs, weight, bias)
+        ctx.save_for_backward(xs, weight)
+        ctx.has_bias = bias is not None
+        ctx.x_shape = x.shape
+        return y.reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, weight = ctx.saved_tensors
+        gys = gy.reshape(-1, gy.shape[-1]).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = native().linear_bf16_bwd_input(gys, weight).reshape(ctx.x_shape)
+        if ctx.needs_input_grad[1]:
+            gw = native().linear_bf16_bwd_weight(gys, xs)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            flops = 2.0 * gys.shape[0] * weight.shape[0] * weight.shape[1]
+            gb = (gys.sum(0) if flops >= _LIB_LIN_THRESH
+                  else native().colsum_f32(gys))
+        return gx, gw, gb
+
+
+# SLK_GEMM=bf16 makes "bf16" the default `compute` of linear() and
+# lora_linear(): the calls that otherwise go to the platform BLAS take the
+# bf16-operand kernels instead (profiles/SUMMARY.md "bf16 MFMA GEMM").
+_GEMM_DEFAULT = "bf16" if os.environ.get("SLK_GEMM", "") == "bf16" else "fp32"
+
+
+def _bf16_fail(x, weight) -> Optional[str]:
+    """the condition of linear_bf16_ok that x, weight miss, or None"""
+    if not (torch.is_tensor(x) and torch.is_tensor(weight)
+            and x.is_cuda and weight.is_cuda):
+        return "x and weight must be CUDA tensors"
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        return "x and weight must be float32"
+    if weight.dim() != 2 or not weight.is_contiguous():
+        return "weight must be a dense [N, K] matrix"
+    n, k = weight.shape
+    if x.dim() < 1 or x.shape[-1] != k:
+        return f"x must be [..., K={k}]"
+    if k % 8 or n % 8 or k == 0 or n == 0:
+        return f"K={k} and N={n} must be positive multiples of 8"
+    if x.numel() == 0:
+        return "x must have at least one row"
+    if x.data_ptr() % 16 or weight.data_ptr() % 16:
+        return "data pointers must be 16-byte aligned"
+    return None
+
+
+def linear_bf16_ok(x, weight) -> bool:
+    """bf16 GEMM precondition: fp32 CUDA tensors, weight dense [N, K],
+    x [..., K] with at least one row, K % 8 == 0, N % 8 == 0, 16-byte-aligned
+    data pointers.  The row count M is free."""
+    return _bf16_fail(x, weight) is None
+
+
+def _takes_bf16(x, weight, compute) -> bool:
+    """does this Linear-shaped product run on the bf16 kernels?  An explicit
+    compute="bf16" must (ValueError if it cannot); the SLK_GEMM=bf16 default
+    takes only the calls that would otherwise go to the platform BLAS."""
+    if compute not in (None, "fp32", "bf16"):
+        raise ValueError(f"compute must be None, 'fp32' or 'bf16', got {compute!r}")
+    if compute == "bf16":
+        why = _bf16_fail(x, weight)
+        if why is not None:
+            raise ValueError(f"compute='bf16': {why}")
+        return True
+    if compute == "fp32" or _GEMM_DEFAULT != "bf16":
+        return False
+    rows = x.numel() // max(x.shape[-1], 1)
+    return (2.0 * rows * weight.shape[0] * weight.shape[1] >= _LIB_LIN_THRESH
+            and linear_bf16_ok(x, weight))
+
+
+def linear(x, weight, bias=None, compute=None):
+    """compute: "fp32" (the fp32 routes), "bf16" (bf16 multiplier operands,
+    any size linear_bf16_ok admits), None (the module default: "fp32", or
+    under SLK_GEMM=bf16 the bf16 kernels for the platform-BLAS-sized calls)."""
+    if _takes_bf16(x, weight, compute):
+        return Bf16LinearFn.apply(x, weight, bias)
     rows = x.numel() // x.shape[-1]
     if 2.0 * rows * weight.shape[0] * weight.shape[1] >= _LIB_LIN_THRESH:
         return _F.linear(x, weight, bias)
@@ -408,16 +507,20 @@ def dropout(x, p, training=True):
 class LoraLinearFn(Function):
     """out = x W^T + b + scaling * (dropout(x) A^T) B^T.  The base product and
     g @ W keep the route linear() gives them (platform BLAS above
-    _LIB_LIN_THRESH, the MFMA GEMM below); everything else is one launch
+    _LIB_LIN_THRESH, the MFMA GEMM below, the bf16-operand GEMM where
+    `bf16` says so); everything else stays fp32 and is one launch
     forward (lora_fwd, in place on the base output) and three backward
     (lora_bwd: rows, weight gradients, slab sum).  Saves x, W, A, B, xa [M,r]
     and the one-element offset the forward read: no xd, mask or delta."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, lora_A, lora_B, scaling, p, seed, offset_t):
+    def forward(ctx, x, weight, bias, lora_A, lora_B, scaling, p, seed, offset_t,
+                bf16=False):
         xs = x.reshape(-1, x.shape[-1]).contiguous()
         lib = 2.0 * xs.shape[0] * weight.shape[0] * weight.shape[1] >= _LIB_LIN_THRESH
-        if lib:
+        if bf16:
+            y = native().linear_bf16_fwd(xs, weight, bias)
+        elif lib:
             y = _F.linear(xs, weight, bias)
         else:
             y = native().linear_fwd(xs, weight, bias)
@@ -425,27 +528,33 @@ class LoraLinearFn(Function):
         xa, used = native().lora_fwd(y, xs, lora_A, lora_B, scaling, p, seed,
                                      offset_t)
         ctx.save_for_backward(xs, weight, lora_A, lora_B, xa, used)
-        ctx.args = (scaling, p, seed, lib, bias is not None, x.shape)
+        ctx.args = (scaling, p, seed, lib, bias is not None, x.shape, bf16)
         return y.reshape(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
         xs, weight, lora_A, lora_B, xa, used = ctx.saved_tensors
-        scaling, p, seed, lib, has_bias, x_shape = ctx.args
+        scaling, p, seed, lib, has_bias, x_shape, bf16 = ctx.args
         gys = gy.reshape(-1, gy.shape[-1]).contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = torch.matmul(gys, weight) if lib else _matmul_raw(gys, weight)
+            if bf16:
+                gx = native().linear_bf16_bwd_input(gys, weight)
+            else:
+                gx = torch.matmul(gys, weight) if lib else _matmul_raw(gys, weight)
         gA, gB = native().lora_bwd(gys, xs, lora_A, lora_B, xa, gx, scaling, p,
                                    seed, used)
         if ctx.needs_input_grad[1]:
-            gw = (torch.matmul(gys.t(), xs) if lib
-                  else _matmul_raw(gys, xs, trans_a=True))
+            if bf16:
+                gw = native().linear_bf16_bwd_weight(gys, xs)
+            else:
+                gw = (torch.matmul(gys.t(), xs) if lib
+                      else _matmul_raw(gys, xs, trans_a=True))
         if has_bias and ctx.needs_input_grad[2]:
             gb = gys.sum(0) if lib else native().colsum_f32(gys)
         if gx is not None:
             gx = gx.reshape(x_shape)
-        return gx, gw, gb, gA, gB, None, None, None, None
+        return gx, gw, gb, gA, gB, None, None, None, None, None
 
 
 def lora_ok(x, weight, lora_A, lora_B) -> bool:
@@ -464,9 +573,11 @@ def lora_ok(x, weight, lora_A, lora_B) -> bool:
 
 
 def lora_linear(x, weight, bias, lora_A, lora_B, scaling, dropout_p=0.0,
-                training=False):
+                training=False, compute=None):
     """Linear with a LoRA adapter on the fused kernels; dropout(x) draws from
-    dropout()'s stream: same counter, same keep decisions."""
+    dropout()'s stream: same counter, same keep decisions.  compute: as in
+    linear(), for the base product and its gradients; the adapter is fp32."""
+    bf16 = _takes_bf16(x, weight, compute)
     p = float(dropout_p) if training else 0.0
     if p > 0.0:
         counter = _counter_for(x.device)
@@ -475,7 +586,7 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scaling, dropout_p=0.0,
     else:
         seed, offset_t = 0, None
     return LoraLinearFn.apply(x, weight, bias, lora_A, lora_B, float(scaling),
-                              p, seed, offset_t)
+                              p, seed, offset_t, bf16)
 
 
 class LoraQkvFn(Function):

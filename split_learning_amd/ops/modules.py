@@ -48,9 +48,12 @@ class HipConv2d(nn.Conv2d):
 
 
 class HipLinear(nn.Linear):
+    # hf.linear's `compute`: None (the module default), "fp32" or "bf16"
+    compute = None
+
     def forward(self, x):
         if _use_native("linear", x):
-            return hf.linear(x, self.weight, self.bias)
+            return hf.linear(x, self.weight, self.bias, self.compute)
         return super().forward(x)
 
 
