@@ -67,6 +67,11 @@ class BertEmbeddings(nn.Module):
 
 
 class BertSdpaSelfAttention(nn.Module):
+    # the attention kernels' `compute`: None (the default), "fp32" or "bf16"
+    # (the bf16-operand tiled kernels at every S; ValueError if they cannot
+    # take the call).  The projections have their own (HipLinear.compute).
+    compute = None
+
     def __init__(self, hidden_size, num_attention_heads, dropout_prob):
         super().__init__()
         self.num_attention_heads = num_attention_heads
@@ -88,7 +93,8 @@ class BertSdpaSelfAttention(nn.Module):
         else:
             q, k, v = (self.query(hidden_states), self.key(hidden_states),
                        self.value(hidden_states))
-        if q.dim() == 3 and _heads_attn_route(q, k, v, H):
+        if q.dim() == 3 and (_heads_attn_route(q, k, v, H) or (
+                self.compute == "bf16" and hf.attn_heads_ok(q, k, v, H))):
             # tiled kernels on the projections' [B,S,E] layout: no head
             # permutes; same additive mask as below.  From the packed tensor
             # attention returns one packed gradient
@@ -97,19 +103,21 @@ class BertSdpaSelfAttention(nn.Module):
             return hf.attention_heads(q, k, v, H, 1.0 / math.sqrt(hd),
                                       dropout_p=self.dropout.p,
                                       training=self.training,
-                                      key_bias=key_bias, packed=qkv)
+                                      key_bias=key_bias, packed=qkv,
+                                      compute=self.compute)
         q = q.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         k = k.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         v = v.view(B, S, H, hd).permute(0, 2, 1, 3).reshape(B * H, S, hd).contiguous()
         if attention_mask is None:
-            ctx = attention_core(q, k, v, dropout_p=self.dropout.p, training=self.training)
+            ctx = attention_core(q, k, v, dropout_p=self.dropout.p,
+                                 training=self.training, compute=self.compute)
         else:
             # [B,S] mask, 1 = token, 0 = pad (any dtype): the reference adds
             # (1 - mask) * -10000 to the scaled scores before the softmax
             key_bias = (1.0 - attention_mask.to(torch.float32)) * -10000.0
             ctx = attention_core(q, k, v, dropout_p=self.dropout.p,
                                  training=self.training, key_bias=key_bias,
-                                 heads=H)
+                                 heads=H, compute=self.compute)
         return ctx.reshape(B, H, S, hd).permute(0, 2, 1, 3).reshape(B, S, E)
 
 

@@ -29,17 +29,19 @@ SOURCES = [
     "loss.hip",
     "attention.hip",
     "attention_tiled.hip",
+    "attention_tiled_bf16.hip",
     "lora.hip",
     "optim.hip",
     "bindings.cpp",
 ]
 
-# per-source device flags.  attention_tiled.hip, lora.hip: no packed-fp32
+# per-source device flags.  attention_tiled*.hip, lora.hip: no packed-fp32
 # instructions (v_pk_mul_f32 and kin) for their float4 accumulator rescales;
 # scalar fp32 ops only, like their MFMA math.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "attention_tiled.hip": _NO_PK_F32,
+    "attention_tiled_bf16.hip": _NO_PK_F32,
     "lora.hip": _NO_PK_F32,
 }
 

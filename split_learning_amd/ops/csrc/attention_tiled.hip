@@ -118,13 +118,14 @@
 //   attn_tiled_bwd_dkv_kernel   64   232    48      33280        0      1
 // The compiler spends registers on hoisted LDS addresses and batched LDS
 // reads; occupancy is register-bound, not LDS-bound (160 KB per CU).
-#include <type_traits>
-
-#include "torch_util.h"
+//
+// The argument block, the layouts' addressing, the causal block order and the
+// template dispatch live in attention_tiled.h, shared with the bf16-operand
+// kernels of attention_tiled_bf16.hip; the host functions below launch those
+// instead when their `bf16` argument is set (same checks, same outputs).
+#include "attention_tiled.h"
 
 namespace slk {
-
-constexpr int AT_TILE = 64;   // rows per block tile and keys per walked tile
 
 __device__ __forceinline__ int at_sw(int row) {
   return 2 * ((row & 3) | ((row & 4) << 1) | ((row & 8) >> 1));
@@ -137,45 +138,6 @@ __device__ __forceinline__ int at_phys(int row, int col) {
 
 __device__ __forceinline__ f32x4 at_mfma(float a, float b, f32x4 acc) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-}
-
-// sum / max over the four 16-lane groups that share a row
-__device__ __forceinline__ float at_group_sum(float x) {
-  x += __shfl_xor(x, 16, 64);
-  return x + __shfl_xor(x, 32, 64);
-}
-__device__ __forceinline__ float at_group_max(float x) {
-  x = fmaxf(x, __shfl_xor(x, 16, 64));
-  return fmaxf(x, __shfl_xor(x, 32, 64));
-}
-
-__device__ __forceinline__ uint32_t at_rng_stream(uint64_t seed, uint64_t offset) {
-  return (uint32_t)(slk_mix64(seed ^ slk_mix64(offset)) >> 32);  // = attn_fwd_kernel
-}
-
-// One operand's strides in floats (head-strided layout only).
-struct AtStride {
-  long batch;
-  int row;
-};
-
-// One block's [S][HD] slice of an operand: its first element and the distance
-// between rows.  Contiguous [BH,S,HD]: the distance is the constant HD and
-// folds into the address arithmetic as before.  Head-strided: b and h are
-// block-uniform, so the slice base is scalar arithmetic done once per operand.
-template <class T>
-struct AtSlice {
-  T* p;
-  int ld;
-};
-
-template <int HD, bool HEADS, class T>
-__device__ __forceinline__ AtSlice<T> at_slice(T* p, const AtStride& st, int bh,
-                                               int heads, int S) {
-  if constexpr (HEADS)
-    return {p + (long)(bh / heads) * st.batch + (bh % heads) * HD, st.row};
-  else
-    return {p + (long)bh * S * HD, HD};
 }
 
 // One [64][HD] tile on its way global -> registers -> LDS.  A thread moves
@@ -248,61 +210,6 @@ __device__ __forceinline__ void at_gemm_relabel(f32x4 (&acc)[HD / 16],
                           w[j][r], acc[db]);
     }
   }
-}
-
-struct AtArgs {
-  const float* q;
-  const float* k;
-  const float* v;
-  const float* key_bias;   // [BH/heads, S] or null
-  float* out;              // fwd: written; bwd: read
-  float* lse;              // [BH,S] fwd: written; bwd: read
-  const float* gout;       // bwd
-  float* delta;            // [BH,S] dq kernel writes, dkv kernel reads
-  float* gq;
-  float* gk;
-  float* gv;
-  const long* offset_in;   // dropout counter (fwd: live; bwd: the saved copy)
-  long* offset_out;        // fwd: the offset it read
-  uint64_t seed;
-  int S, heads;
-  float scale, p, inv_keep;
-  // head-strided instantiations only (the contiguous ones never read them)
-  AtStride sq, sk, sv, so, sgo, sgq, sgk, sgv;
-};
-
-// the walked tile's additive row: bias (or 0) at keys < S, -inf past S
-template <bool BIAS>
-__device__ __forceinline__ float at_key_bias(const float* __restrict__ kbr,
-                                             int key, int S) {
-  if (key >= S) return -INFINITY;
-  return BIAS ? kbr[key] : 0.f;
-}
-
-// Which (tile, bh) a block takes; the grid is (tiles, BH) in both modes.
-// Non-causal: the block indices as they are.  Causal: a forward / dq block of
-// query tile qt walks qt + 1 key tiles and a dkv block of key tile kt walks
-// tiles - kt query tiles, so the blocks are taken in launch order level by
-// level: all bh of the heaviest tile first (heavy_last: that is the last
-// tile, else tile 0), then all bh of the next.  Neighbours in launch order
-// then carry equal work, whatever rule spreads them over the chip, and the
-// light blocks fill the tail.  (Tile-fastest orders put every bh's heavy
-// tile on the same launch-order residue: profiles/SUMMARY.md.)
-struct AtBlock {
-  int tile, bh;
-};
-template <bool CAUSAL>
-__device__ __forceinline__ AtBlock at_block(bool heavy_last) {
-  if (!CAUSAL) return {(int)blockIdx.x, (int)blockIdx.y};
-  const unsigned long id = (unsigned long)blockIdx.y * gridDim.x + blockIdx.x;
-  const int level = (int)(id / gridDim.y);
-  return {heavy_last ? (int)gridDim.x - 1 - level : level, (int)(id % gridDim.y)};
-}
-
-// Causal mode, diagonal tile (query tile == key tile): tile-local key `key`
-// is hidden from tile-local query row `row` when it lies in the row's future.
-__device__ __forceinline__ bool at_hidden(bool diagonal, int row, int key) {
-  return diagonal && key > row;
 }
 
 template <int HD, bool DROPOUT, bool BIAS, bool HEADS, bool CAUSAL>
@@ -626,13 +533,6 @@ static at::Tensor at_operand(const at::Tensor& t, const at::Tensor& like,
   return tc;
 }
 
-struct AtProblem {
-  long BH;
-  int S, hd;
-  bool drop, bias, causal;
-  at::Tensor kb, off;
-};
-
 // the rules both layouts share, on the problem's (BH, S, hd)
 static AtProblem at_check_dims(const at::Tensor& q, long BH, long S, long hd,
                                double p,
@@ -675,31 +575,6 @@ static AtProblem at_check(const at::Tensor& q, double p,
                        heads, who);
 }
 
-#define SLK_AT_DISPATCH(KERNEL, HEADS, pr, grid, stream, args)                 \
-  do {                                                                         \
-    auto go = [&](auto hd_c, auto drop_c, auto bias_c, auto causal_c) {        \
-      hipLaunchKernelGGL(                                                      \
-          (KERNEL<decltype(hd_c)::value, decltype(drop_c)::value,              \
-                  decltype(bias_c)::value, HEADS,                              \
-                  decltype(causal_c)::value>),                                 \
-          grid, dim3(256), 0, stream, args);                                   \
-    };                                                                         \
-    auto go_c = [&](auto hd_c, auto drop_c, auto bias_c) {                     \
-      if ((pr).causal) go(hd_c, drop_c, bias_c, std::true_type{});             \
-      else go(hd_c, drop_c, bias_c, std::false_type{});                        \
-    };                                                                         \
-    auto go_b = [&](auto hd_c, auto drop_c) {                                  \
-      if ((pr).bias) go_c(hd_c, drop_c, std::true_type{});                     \
-      else go_c(hd_c, drop_c, std::false_type{});                              \
-    };                                                                         \
-    auto go_d = [&](auto hd_c) {                                               \
-      if ((pr).drop) go_b(hd_c, std::true_type{});                             \
-      else go_b(hd_c, std::false_type{});                                      \
-    };                                                                         \
-    if ((pr).hd == 32) go_d(std::integral_constant<int, 32>{});                \
-    else go_d(std::integral_constant<int, 64>{});                              \
-  } while (0)
-
 static AtArgs at_args(const AtProblem& pr, const at::Tensor& q,
                       const at::Tensor& k, const at::Tensor& v, double scale,
                       double p, int64_t seed, int64_t heads) {
@@ -724,7 +599,8 @@ std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor& q, const at::Tensor& k,
                                        double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       int64_t heads, bool is_causal) {
+                                       int64_t heads, bool is_causal,
+                                       bool bf16) {
   const char* who = "attn_tiled_fwd";
   AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
   pr.causal = is_causal;
@@ -740,7 +616,8 @@ std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor& q, const at::Tensor& k,
   a.offset_out = pr.drop ? used.data_ptr<long>() : nullptr;
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_fwd_kernel, false, pr, grid, stream, a);
+  if (bf16) at_bf16_fwd(false, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_fwd_kernel, false, pr, grid, stream, a);
   return {out, lse, used};
 }
 
@@ -751,7 +628,8 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor& gout, const at::Tensor&
                                        double scale, double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       int64_t heads, bool is_causal) {
+                                       int64_t heads, bool is_causal,
+                                       bool bf16) {
   const char* who = "attn_tiled_bwd";
   if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
   AtProblem pr = at_check(q, p, offset, key_bias, heads, who);
@@ -779,9 +657,11 @@ std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor& gout, const at::Tensor&
   a.gv = gv.data_ptr<float>();
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, false, pr, grid, stream, a);
+  if (bf16) at_bf16_bwd_dq(false, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, false, pr, grid, stream, a);
   // same stream: delta is complete before the dkv kernel starts
-  SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, false, pr, grid, stream, a);
+  if (bf16) at_bf16_bwd_dkv(false, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, false, pr, grid, stream, a);
   return {gq, gk, gv};
 }
 
@@ -839,7 +719,7 @@ std::vector<at::Tensor> attn_heads_fwd(const at::Tensor& q, const at::Tensor& k,
                                        double scale, double p, int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       bool is_causal) {
+                                       bool is_causal, bool bf16) {
   const char* who = "attn_heads_fwd";
   AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
   pr.causal = is_causal;
@@ -857,7 +737,8 @@ std::vector<at::Tensor> attn_heads_fwd(const at::Tensor& q, const at::Tensor& k,
   a.offset_out = pr.drop ? used.data_ptr<long>() : nullptr;
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_fwd_kernel, true, pr, grid, stream, a);
+  if (bf16) at_bf16_fwd(true, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_fwd_kernel, true, pr, grid, stream, a);
   return {out, lse, used};
 }
 
@@ -872,7 +753,7 @@ std::vector<at::Tensor> attn_heads_bwd(const at::Tensor& gout, const at::Tensor&
                                        int64_t seed,
                                        c10::optional<at::Tensor> offset,
                                        c10::optional<at::Tensor> key_bias,
-                                       bool is_causal) {
+                                       bool is_causal, bool bf16) {
   const char* who = "attn_heads_bwd";
   if (offset.has_value() && offset->numel() == 0) offset = c10::nullopt;
   AtProblem pr = at_heads_check(q, heads, p, offset, key_bias, who);
@@ -922,9 +803,11 @@ std::vector<at::Tensor> attn_heads_bwd(const at::Tensor& gout, const at::Tensor&
   a.gv = g[2].data_ptr<float>();
   const dim3 grid(ceil_div(pr.S, AT_TILE), (unsigned)pr.BH);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, true, pr, grid, stream, a);
+  if (bf16) at_bf16_bwd_dq(true, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_bwd_dq_kernel, true, pr, grid, stream, a);
   // same stream: delta is complete before the dkv kernel starts
-  SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, true, pr, grid, stream, a);
+  if (bf16) at_bf16_bwd_dkv(true, pr, grid, stream, a);
+  else SLK_AT_DISPATCH(attn_tiled_bwd_dkv_kernel, true, pr, grid, stream, a);
   return g;
 }
 

@@ -99,23 +99,25 @@ at::Tensor attn_softmax_bwd(const at::Tensor&, const at::Tensor&,
 std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, double, double, int64_t,
                                        c10::optional<at::Tensor>,
-                                       c10::optional<at::Tensor>, int64_t, bool);
+                                       c10::optional<at::Tensor>, int64_t, bool,
+                                       bool);
 std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
                                        double, double, int64_t,
                                        c10::optional<at::Tensor>,
-                                       c10::optional<at::Tensor>, int64_t, bool);
+                                       c10::optional<at::Tensor>, int64_t, bool,
+                                       bool);
 std::vector<at::Tensor> attn_heads_fwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, int64_t, double, double,
                                        int64_t, c10::optional<at::Tensor>,
-                                       c10::optional<at::Tensor>, bool);
+                                       c10::optional<at::Tensor>, bool, bool);
 std::vector<at::Tensor> attn_heads_bwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
                                        int64_t, double, double, int64_t,
                                        c10::optional<at::Tensor>,
-                                       c10::optional<at::Tensor>, bool);
+                                       c10::optional<at::Tensor>, bool, bool);
 // lora.hip
 std::vector<at::Tensor> lora_fwd(at::Tensor, const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, double, double, int64_t,
@@ -253,21 +255,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_tiled_fwd", &slk::attn_tiled_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
         py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
-        py::arg("heads") = 1, py::arg("is_causal") = false);
+        py::arg("heads") = 1, py::arg("is_causal") = false,
+        py::arg("bf16") = false);
   m.def("attn_tiled_bwd", &slk::attn_tiled_bwd, py::arg("gout"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"),
         py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0,
         py::arg("offset") = py::none(), py::arg("key_bias") = py::none(),
-        py::arg("heads") = 1, py::arg("is_causal") = false);
+        py::arg("heads") = 1, py::arg("is_causal") = false,
+        py::arg("bf16") = false);
   m.def("attn_heads_fwd", &slk::attn_heads_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("heads"), py::arg("scale"), py::arg("p") = 0.0,
         py::arg("seed") = 0, py::arg("offset") = py::none(),
-        py::arg("key_bias") = py::none(), py::arg("is_causal") = false);
+        py::arg("key_bias") = py::none(), py::arg("is_causal") = false,
+        py::arg("bf16") = false);
   m.def("attn_heads_bwd", &slk::attn_heads_bwd, py::arg("gout"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"),
         py::arg("heads"), py::arg("scale"), py::arg("p") = 0.0,
         py::arg("seed") = 0, py::arg("offset") = py::none(),
-        py::arg("key_bias") = py::none(), py::arg("is_causal") = false);
+        py::arg("key_bias") = py::none(), py::arg("is_causal") = false,
+        py::arg("bf16") = false);
   m.def("lora_fwd", &slk::lora_fwd, py::arg("y"), py::arg("x"),
         py::arg("lora_A"), py::arg("lora_B"), py::arg("scaling"),
         py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = py::none());

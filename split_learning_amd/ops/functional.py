@@ -14,6 +14,12 @@ gradients stay fp32, and only the multiplier's operands are rounded to bf16
 then the fp32 sum of exact products of the rounded operands; what that does to
 a model's accuracy beyond the recorded BERT loss is not measured.
 
+The tiled attention kernels have the same opt-in (attention_tiled() and
+attention_heads() compute="bf16", or SLK_ATTN=bf16 for the calls that take the
+tiled route anyway; csrc/attention_tiled_bf16.hip): q, k, v, the upstream
+gradient, the probabilities and dS are rounded to bf16 as MFMA operands; the
+scores' sum, the softmax, lse, delta and every accumulator stay fp32.
+
 Kernel-side entry points live in split_learning_amd/ops/csrc/ and are exported by
 the in-tree _sl_kernels extension (see ops/__init__.py loading policy).
 """
@@ -843,40 +849,73 @@ class AttnTiledFn(Function):
     Saves q, k, v, out, lse [BH,S] and that one-element offset tensor (plus
     the [B,S] bias): nothing of size S^2."""
 
-    @staticmethod
-    def forward(ctx, q, k, v, scale, p, seed, offset_t, key_bias=None,
+    bf16 = False   # which kernels: AttnTiledBf16Fn sets it
+
+    @classmethod
+    def forward(cls, ctx, q, k, v, scale, p, seed, offset_t, key_bias=None,
                 heads=1, is_causal=False):
         out, lse, used = native().attn_tiled_fwd(q, k, v, scale, p, seed,
                                                  offset_t, key_bias, heads,
-                                                 is_causal)
+                                                 is_causal, cls.bf16)
         ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
         ctx.args = (scale, float(p), seed, heads, is_causal)
         return out
 
-    @staticmethod
-    def backward(ctx, gy):
+    @classmethod
+    def backward(cls, ctx, gy):
         q, k, v, out, lse, used, key_bias = ctx.saved_tensors
         scale, p, seed, heads, is_causal = ctx.args
         gq, gk, gv = native().attn_tiled_bwd(gy, q, k, v, out, lse, scale, p,
                                              seed, used, key_bias, heads,
-                                             is_causal)
+                                             is_causal, cls.bf16)
         return gq, gk, gv, None, None, None, None, None, None, None
+
+
+class AttnTiledBf16Fn(AttnTiledFn):
+    """AttnTiledFn on the bf16-operand kernels (attention_tiled_bf16.hip):
+    same arguments, same saved state, same dropout decisions."""
+    bf16 = True
+
+
+# SLK_ATTN=bf16 makes "bf16" the default `compute` of attention_tiled() and
+# attention_heads(): the calls that take the tiled route anyway run its
+# bf16-operand kernels.  It never changes which route a caller takes.
+_ATTN_DEFAULT = "bf16" if os.environ.get("SLK_ATTN", "") == "bf16" else "fp32"
+
+
+def _attn_bf16(compute, ok: bool, rule: str) -> bool:
+    """do the tiled kernels run with bf16 operands?  compute as in linear();
+    an explicit "bf16" must (ValueError naming the precondition, `rule`, if
+    `ok` does not hold); the SLK_ATTN=bf16 default never raises."""
+    if compute not in (None, "fp32", "bf16"):
+        raise ValueError(f"compute must be None, 'fp32' or 'bf16', got {compute!r}")
+    if compute == "bf16":
+        if not ok:
+            raise ValueError(f"compute='bf16': needs {' '.join(rule.split())}")
+        return True
+    return compute is None and _ATTN_DEFAULT == "bf16" and ok
 
 
 def attn_tiled_ok(q, k, v) -> bool:
     """tiled path precondition: three [BH, S, hd in {32, 64}] fp32 CUDA
     tensors of one shape; any S >= 1."""
-    return (q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
+    return (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)
+            and q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
             and q.shape[2] in (32, 64) and q.shape[1] >= 1
             and k.shape == q.shape and v.shape == q.shape
             and k.dtype == q.dtype and v.dtype == q.dtype)
 
 
 def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
-                    key_bias=None, heads=1, is_causal=False):
+                    key_bias=None, heads=1, is_causal=False, compute=None):
     """attention() on the tiled kernels: same arguments, same dropout counter
     and keep decisions, any S.  is_causal: query row i attends to keys <= i
-    (the kernels skip the key tiles above the diagonal; no mask tensor)."""
+    (the kernels skip the key tiles above the diagonal; no mask tensor).
+    compute: "fp32", "bf16" (the bf16-operand kernels; ValueError unless
+    attn_tiled_ok holds) or None (the default: "fp32", or "bf16" under
+    SLK_ATTN=bf16)."""
+    fn = AttnTiledBf16Fn if _attn_bf16(
+        compute, attn_tiled_ok(q, k, v), attn_tiled_ok.__doc__) else AttnTiledFn
     p = float(dropout_p) if training else 0.0
     if p > 0.0:
         counter = _counter_for(q.device)
@@ -884,10 +923,9 @@ def attention_tiled(q, k, v, scale, dropout_p=0.0, training=False,
         seed, offset_t = _DROPOUT_STATE["seed"], counter
     else:
         seed, offset_t = 0, None
-    return AttnTiledFn.apply(q.contiguous(), k.contiguous(), v.contiguous(),
-                             float(scale), p, seed, offset_t,
-                             _key_bias_arg(key_bias), int(heads),
-                             bool(is_causal))
+    return fn.apply(q.contiguous(), k.contiguous(), v.contiguous(),
+                    float(scale), p, seed, offset_t, _key_bias_arg(key_bias),
+                    int(heads), bool(is_causal))
 
 
 class AttnHeadsFn(Function):
@@ -901,26 +939,34 @@ class AttnHeadsFn(Function):
     Saves the operand views, out, lse [B*heads,S], the used-offset tensor and
     the bias: nothing of size S^2."""
 
-    @staticmethod
-    def forward(ctx, x, k, v, heads, scale, p, seed, offset_t, key_bias=None,
-                is_causal=False):
+    bf16 = False   # which kernels: AttnHeadsBf16Fn sets it
+
+    @classmethod
+    def forward(cls, ctx, x, k, v, heads, scale, p, seed, offset_t,
+                key_bias=None, is_causal=False):
         ctx.packed = k is None
         q, k, v = x.split(x.shape[-1] // 3, dim=-1) if ctx.packed else (x, k, v)
         out, lse, used = native().attn_heads_fwd(q, k, v, heads, scale, p, seed,
-                                                 offset_t, key_bias, is_causal)
+                                                 offset_t, key_bias, is_causal,
+                                                 cls.bf16)
         ctx.save_for_backward(q, k, v, out, lse, used, key_bias)
         ctx.args = (heads, scale, float(p), seed, is_causal)
         return out
 
-    @staticmethod
-    def backward(ctx, gy):
+    @classmethod
+    def backward(cls, ctx, gy):
         q, k, v, out, lse, used, key_bias = ctx.saved_tensors
         heads, scale, p, seed, is_causal = ctx.args
         g = native().attn_heads_bwd(gy, q, k, v, out, lse, heads, scale, p,
-                                    seed, used, key_bias, is_causal)
+                                    seed, used, key_bias, is_causal, cls.bf16)
         if ctx.packed:
             return (g[3],) + (None,) * 9
         return g[0], g[1], g[2], None, None, None, None, None, None, None
+
+
+class AttnHeadsBf16Fn(AttnHeadsFn):
+    """AttnHeadsFn on the bf16-operand kernels (attention_tiled_bf16.hip)."""
+    bf16 = True
 
 
 def attn_heads_ok(q, k, v, heads) -> bool:
@@ -928,7 +974,8 @@ def attn_heads_ok(q, k, v, heads) -> bool:
     tensors of one shape, hd in {32, 64}, S >= 1, B * heads within the grid;
     unit last stride, row and batch strides multiples of 4 floats and
     16-byte-aligned bases (the kernels move float4s)."""
-    if not (q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
+    if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)
+            and q.is_cuda and q.dim() == 3 and q.dtype == torch.float32
             and heads >= 1 and q.shape[2] % heads == 0
             and q.shape[2] // heads in (32, 64) and q.shape[1] >= 1
             and q.shape[0] * heads <= 65535):
@@ -958,7 +1005,7 @@ def _packed_base(q, k, v, base):
 
 
 def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
-                    key_bias=None, packed=None, is_causal=False):
+                    key_bias=None, packed=None, is_causal=False, compute=None):
     """attention_tiled() without the head permutes: q, k, v [B,S,E] as the
     projections wrote them (three tensors, or three column views of one packed
     [B,S,3E]), result [B,S,E] as the output projection reads it.  Head h is
@@ -967,7 +1014,11 @@ def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
     there.
 
     packed names the [B,S,3E] tensor q, k, v were split from, for a caller
-    whose q._base is not that tensor (a view of a view reports the root)."""
+    whose q._base is not that tensor (a view of a view reports the root).
+    compute: as in attention_tiled, against attn_heads_ok."""
+    fn = AttnHeadsBf16Fn if _attn_bf16(
+        compute, attn_heads_ok(q, k, v, int(heads)),
+        attn_heads_ok.__doc__) else AttnHeadsFn
     p = float(dropout_p) if training else 0.0
     if p > 0.0:
         counter = _counter_for(q.device)
@@ -978,8 +1029,8 @@ def attention_heads(q, k, v, heads, scale, dropout_p=0.0, training=False,
     base = _packed_base(q, k, v, packed)
     if base is not None:
         q, k, v = base, None, None
-    return AttnHeadsFn.apply(q, k, v, int(heads), float(scale), p, seed,
-                             offset_t, _key_bias_arg(key_bias), bool(is_causal))
+    return fn.apply(q, k, v, int(heads), float(scale), p, seed, offset_t,
+                    _key_bias_arg(key_bias), bool(is_causal))
 
 
 class AttnProbsFn(Function):

@@ -151,6 +151,11 @@ class HipMultiheadAttention(nn.MultiheadAttention):
     (reference src/model/KWT_SPEECHCOMMANDS.py:9, other/.../ViT_CIFAR10.py:7).
     """
 
+    # hf.attention_heads' `compute`: None (the module default), "fp32" or
+    # "bf16".  "bf16" takes the attention_heads route at every S whenever
+    # hf.attn_heads_ok holds, and raises ValueError where it does not.
+    compute = None
+
     def forward(self, query, key, value, **kwargs):  # type: ignore[override]
         # The native path computes plain, key-padded or causal self-attention
         # and returns no weights.  Causal is torch's hint form: is_causal=True
@@ -185,14 +190,15 @@ class HipMultiheadAttention(nn.MultiheadAttention):
                                       dropout_p=self.dropout,
                                       training=self.training,
                                       key_bias=key_bias, packed=qkv,
-                                      is_causal=True)
-        elif _heads_attn_route(q, k, v, H):
+                                      is_causal=True, compute=self.compute)
+        elif self.compute == "bf16" or _heads_attn_route(q, k, v, H):
             # tiled kernels on qkv's own layout: the three column views go in
             # as they are, the context comes out as out_proj reads it
             ctxv = hf.attention_heads(q, k, v, H, scale,
                                       dropout_p=self.dropout,
                                       training=self.training,
-                                      key_bias=key_bias, packed=qkv)
+                                      key_bias=key_bias, packed=qkv,
+                                      compute=self.compute)
         elif S <= 128 and hd <= 64 and (hd & (hd - 1)) == 0 \
                 and "fattn" not in _DBG_TORCH \
                 and _fused_attn_worth_it(B * H, S, self.dropout, self.training):
@@ -312,24 +318,32 @@ def _causal_heads_ok(x, heads) -> bool:
 
 def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
                    scale: Optional[float] = None, key_bias=None,
-                   heads: int = 1, is_causal: bool = False):
+                   heads: int = 1, is_causal: bool = False, compute=None):
     """scaled-dot-product attention on [B*H, S, hd] tensors via HIP kernels.
 
     key_bias ([B, S] additive float, B = q.shape[0] // heads) is added to the
     scaled scores of every head and query row of its sample before the
     softmax: a padding mask.  Without it every route is the unmasked one.
-    is_causal: query row i attends to keys <= i, with or without key_bias."""
+    is_causal: query row i attends to keys <= i, with or without key_bias.
+    compute: hf.attention_tiled's.  "bf16" takes the tiled route at every S
+    hf.attn_tiled_ok admits, with or without key_bias / is_causal, and raises
+    ValueError otherwise; None and "fp32" leave the routes as they are."""
     hd = q.shape[-1]
     s = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if compute == "bf16":
+        return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
+                                  training=training, key_bias=key_bias,
+                                  heads=heads, is_causal=is_causal,
+                                  compute=compute)
     if is_causal:
         return _attention_core_causal(q, k, v, dropout_p, training, s,
-                                      key_bias, heads)
+                                      key_bias, heads, compute)
     if key_bias is not None:
         return _attention_core_biased(q, k, v, dropout_p, training, s,
-                                      key_bias, heads)
+                                      key_bias, heads, compute)
     if _tiled_attn_route(q, k, v):
         return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
-                                  training=training)
+                                  training=training, compute=compute)
     if (_use_native("attn", q) and "fattn" not in _DBG_TORCH and q.dim() == 3
             and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
             and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
@@ -349,7 +363,8 @@ def attention_core(q, k, v, dropout_p: float = 0.0, training: bool = False,
     return torch.matmul(probs, v)
 
 
-def _attention_core_causal(q, k, v, dropout_p, training, s, key_bias, heads):
+def _attention_core_causal(q, k, v, dropout_p, training, s, key_bias, heads,
+                           compute=None):
     """attention_core with a causal mask.  The tiled kernels are the only
     native route that can mask causally (they walk the key tiles up to the
     diagonal), so they take every S their operand rule admits; what they
@@ -365,7 +380,7 @@ def _attention_core_causal(q, k, v, dropout_p, training, s, key_bias, heads):
             and hf.attn_tiled_ok(q, k, v)):
         return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
                                   training=training, key_bias=key_bias,
-                                  heads=heads, is_causal=True)
+                                  heads=heads, is_causal=True, compute=compute)
     scores = torch.matmul(q, k.transpose(-1, -2)) * s
     if key_bias is not None:
         scores = (scores.view(BH // heads, heads, S, S)
@@ -378,7 +393,8 @@ def _attention_core_causal(q, k, v, dropout_p, training, s, key_bias, heads):
     return torch.matmul(probs, v)
 
 
-def _attention_core_biased(q, k, v, dropout_p, training, s, key_bias, heads):
+def _attention_core_biased(q, k, v, dropout_p, training, s, key_bias, heads,
+                           compute=None):
     """attention_core with an additive key bias; same three routes."""
     hd = q.shape[-1]
     if q.dim() != 3 or q.shape[0] % heads != 0 or \
@@ -389,7 +405,7 @@ def _attention_core_biased(q, k, v, dropout_p, training, s, key_bias, heads):
     if _tiled_attn_route(q, k, v):
         return hf.attention_tiled(q, k, v, s, dropout_p=dropout_p,
                                   training=training, key_bias=key_bias,
-                                  heads=heads)
+                                  heads=heads, compute=compute)
     if (_use_native("attn", q) and "fattn" not in _DBG_TORCH
             and q.shape[1] <= 128 and hd <= 64 and (hd & (hd - 1)) == 0
             and _fused_attn_worth_it(q.shape[0], q.shape[1], dropout_p,
